@@ -2,8 +2,26 @@
 """Headline benchmark: 5x5 Gaussian blur on a 16384x16384 RGB frame,
 row-partitioned over N MI355X (one process per GPU, RCCL over xGMI).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does what the headline figure needs and nothing else: set-up
+(autotune, halo-schedule / stream probe), W warmup steps, the K timed steps,
+the output dump when --dump-outputs is given, the one JSON line.  --full adds
+everything else this file measures or checks: the transport check, per-step
+device events, stage times, golden verification, the copy roofline and the
+other scopes (below).  The headline fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step) are the same either way; fields that
+only --full fills are null in a plain run.
+
+--dump-outputs DIR writes, after the timed steps, what they left in every
+frame of the stream (this rank's result stripe, the array a caller of
+FrameStream receives from result_stripe()) as DIR/frame<f>.npy (at N > 1:
+frame<f>.rank<r>.npy), float32.  An output above the size budget (64 MB over
+all files) is written as a fixed, seeded sample of its elements.  The frames
+are reloaded from the seed right before the warmup steps, so the same
+arguments give the same inputs, and the same number of steps on them, in
+every run.
 
 One step = one full-frame gaussian5 pass over the distributed frame: every rank
 filters its stripe with the halo rows its neighbours sent (ncclSend/ncclRecv).
@@ -36,7 +54,8 @@ warm single-frame number (resident_warm) and the communication-avoiding deep
 halo (resident_deep: k*2 rows exchanged once per k steps, bit-identical) are
 reported beside it as named scopes, never as `value`.
 
-Order of work (the timed region holds nothing but the K steps):
+Order of work with --full (the timed region holds nothing but the K steps;
+a plain run stops after the timed steps and the dump):
   identity (what RCCL and the runtime report, gathered to rank 0) -> autotune
   (band height x occupancy cap x memory policy, on cold data when the frames
   rotate, each stage's candidates timed round-robin; collective at N > 1:
@@ -94,6 +113,12 @@ def parse():
     ap.add_argument("--channels", type=int, default=3)
     ap.add_argument("--chain", default="gaussian5")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: transport check, per-step device events, stage "
+                         "times, golden verification, copy roofline and the other scopes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write every frame's result stripe as DIR/frame<f>.npy (float32; "
+                         "a fixed seeded sample of the elements where the whole would exceed 64 MB over all files)")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--band", type=int, default=0)
     ap.add_argument("--halo-schedule", default="auto",
@@ -187,6 +212,32 @@ def exchange_cost(before: dict, after: dict, steps: int) -> dict | None:
     return {"exchanges": int(n), "per_step": round(n / max(1, steps), 3), "host_us_per_exchange": round(us / n, 2),
             "group_end_us_per_exchange": round(end / n, 2), "host_us_per_step": round(us / max(1, steps), 2),
             "in_progress_ends": int(after.get("groups_in_progress", 0) - before.get("groups_in_progress", 0))}
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6  # all files of one --dump-outputs run together
+DUMP_SAMPLE_SEED = 20240229  # the sample's element indices: the same in every run and build
+
+
+def dump_outputs(directory: str, arrays: dict, budget_bytes: int) -> dict:
+    """Write each named array as <directory>/<name>.npy in float32, whole when
+    it fits its equal share of budget_bytes, else the elements at seeded
+    random flat indices (sorted; a function of the array's size and name order
+    alone, so two builds sample the same elements).  Returns what was written,
+    per name."""
+    os.makedirs(directory, exist_ok=True)
+    share = max(1, budget_bytes // max(1, len(arrays)) // 4 - 64)  # float32 elements per file, header allowed for
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    written = {}
+    for name, arr in arrays.items():
+        flat = np.ascontiguousarray(arr).reshape(-1)
+        if flat.size > share:
+            idx = np.sort(rng.integers(0, flat.size, size=share, dtype=np.int64))
+            out, what = flat[idx].astype(np.float32), f"sample of {share} of {flat.size} elements"
+        else:
+            out, what = np.asarray(arr, dtype=np.float32), "whole"
+        np.save(os.path.join(directory, name + ".npy"), out)
+        written[name] = {"shape": list(arr.shape), "stored": what}
+    return written
 
 
 def elapsed_s() -> float:
@@ -297,7 +348,7 @@ def main():
     # the frame-stream pattern (4 frames over 2 streams), every word verified;
     # at N = 1 the RCCL communicator sends to and receives from itself ----
     transport = None
-    if ctx.comm is not None and ctx.device:
+    if a.full and ctx.comm is not None and ctx.device:
         transport = dict(parallel.ring_check(ctx, 4 * (-(-R * W * Cc // 4)), frames=4, streams=2, iters=200),
                          peers="self (loopback)" if world == 1 else "ring r -> r+1")
         transport["errors"] = int(max_over_ranks(float(transport["errors"])))
@@ -348,6 +399,9 @@ def main():
     sync_frames = fs.synchronize
     frame_stream = fs.stream_of
 
+    # the tune and the probe stepped the frames: back to the seeded pixels, so
+    # the W + K steps below run on the same inputs in every run (--dump-outputs)
+    fs.load_synthetic(a.seed)
     for i in range(a.warmup):
         step(i)
     sync_frames()
@@ -370,11 +424,19 @@ def main():
     log.info("resident: %.5f ms/step over %d steps (%d frame(s), %d stream(s))", ms_per_step, a.steps, nframes,
              nstreams)
 
+    # ---- what the timed steps computed: every frame's result stripe on this
+    # rank, before anything else steps the frames ----
+    dumped = None
+    if a.dump_outputs:
+        tag = "" if world == 1 else f".rank{rank}"
+        dumped = dump_outputs(a.dump_outputs, {f"frame{k}{tag}": f.result_stripe() for k, f in enumerate(frames)},
+                              DUMP_BUDGET_BYTES // world)
+
     # per-step device time distribution: an event on the step's stream after
     # each step, max(K, 20) steps, untimed by the host clock above (the events
     # themselves add a few us a step)
     step_ms = None
-    if dev and rows > 0:
+    if a.full and dev and rows > 0:
         n_ev = max(a.steps, 20)
         sync()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
@@ -395,10 +457,12 @@ def main():
         assert all(frame_stream(i) is frame_stream(i + w) for i in range(n_ev - w + 1))
         step_ms = stats([ev[i].elapsed_time(ev[i + w]) / w for i in range(n_ev - w + 1)])
     # device-event stage times of one step of frame 0 on rank 0
-    dp.engine.stage_timing = True
-    step(0)
-    dp.synchronize()
-    stages = {"resident": {k: round(v, 4) for k, v in dp.stage_times().items() if k in ("compute", "halo")}}
+    stages = {}
+    if a.full:
+        dp.engine.stage_timing = True
+        step(0)
+        dp.synchronize()
+        stages["resident"] = {k: round(v, 4) for k, v in dp.stage_times().items() if k in ("compute", "halo")}
 
     def ramp(ms_target=30.0):
         """GPU clock ramp before a timed scope: the host-side checks between
@@ -424,7 +488,9 @@ def main():
         return np.concatenate(parts, axis=0)
 
     verify = None
-    if not a.no_verify and a.self_halo:
+    if not a.full:
+        pass  # a plain run leaves verified_vs_golden null
+    elif not a.no_verify and a.self_halo:
         n_it = 2 if iterable else 1
         dp.load_synthetic(a.seed)
         dp.run(n_it)
@@ -469,7 +535,7 @@ def main():
     bytes_out = rows * W * pinfo["cout"]
     step_bytes = bytes_in + bytes_out
     copy = None
-    if dev and rows > 0:
+    if a.full and dev and rows > 0:
         n = step_bytes // 2
         copy = C.copy_roofline(ctx.gpu, n, max(1, -(-3 * MALL_BYTES // (2 * n))), 20)
         torch.cuda.empty_cache()
@@ -486,6 +552,8 @@ def main():
         "steps": a.steps,
         "warmup": a.warmup,
         "ms_per_step": round(ms_per_step, 5),
+        "full": bool(a.full),
+        "outputs": None if dumped is None else {"dir": a.dump_outputs, "files": dumped},
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None if BASELINE_MPX is None else round(mpx / BASELINE_MPX, 3),
@@ -891,9 +959,10 @@ def main():
                 hl["e2e_frac_of_floor"] = round(hl["both_ms"] / ems, 3) if ems > 0 else None
                 scopes["e2e"]["host_link_rank0"] = hl
 
+    extra_scopes = (("resident_warm", scope_warm), ("resident_deep", scope_deep), ("dist", scope_dist),
+                    ("ref_window", scope_ref), ("e2e", scope_e2e)) if a.full else ()
     try:
-        for name, fn in (("resident_warm", scope_warm), ("resident_deep", scope_deep), ("dist", scope_dist),
-                         ("ref_window", scope_ref), ("e2e", scope_e2e)):
+        for name, fn in extra_scopes:
             guarded(name, fn)
     except Exception as e:  # noqa: BLE001 - a collective between scopes failed (a peer died or stalled)
         log.error("extra scopes abandoned: %s: %s", type(e).__name__, e)

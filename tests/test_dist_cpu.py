@@ -109,7 +109,7 @@ def test_bench_host_backend_multi_rank(tmp_path, nproc, depth):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus",
            str(nproc), "--steps", "7" if depth else "3", "--warmup", "1", "--width", "200", "--height", "96",
-           "--backend", "host", "--dist-steps", "2", "--halo-depth", str(depth)]
+           "--backend", "host", "--full", "--dist-steps", "2", "--halo-depth", str(depth)]
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout + r.stderr
@@ -125,6 +125,54 @@ def test_bench_host_backend_multi_rank(tmp_path, nproc, depth):
     deep = rec["scopes"]["resident_deep"]
     if depth:
         assert deep["halo_depth"] == depth and deep["steps"] % depth == 0
+
+
+def test_bench_plain_run_dumps_timed_outputs(tmp_path, C):
+    """A plain bench.py run (no --full) ends after the timed steps: nothing is
+    verified and no other scope runs.  --dump-outputs writes what the W + K
+    steps left in the frame: the seeded pixels through the golden path W + K
+    times."""
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+           "--width", "70", "--height", "40", "--seed", "5", "--backend", "host", "--dump-outputs", str(out)]
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    for k in ["metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"]:
+        assert k in rec
+    assert rec["full"] is False and rec["steps"] == 3 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert rec["verified_vs_golden"] is None and rec["transport_check"] is None and rec["copy_roofline"] is None
+    assert set(rec["scopes"]) == {"resident"} and rec["budget"]["skipped"] == []
+    assert sorted(p.name for p in out.iterdir()) == ["frame0.npy"]
+    got = np.load(out / "frame0.npy")
+    ref = C.synth_rows(5, 70, 3, 0, 40)
+    for _ in range(2 + 3):
+        ref = C.golden_apply(ref, "gaussian5", "reflect101", True)
+    assert got.dtype == np.float32 and got.shape == ref.shape and (got == ref).all()
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """Outputs above the size budget are stored as the same seeded sample of
+    their elements in every run, all files together inside the budget."""
+    import bench
+
+    rng = np.random.default_rng(3)
+    arrays = {"a": rng.integers(0, 256, size=(37, 53, 3), dtype=np.uint8),
+              "b": rng.integers(0, 256, size=(11, 7), dtype=np.uint8)}
+    budget = 8000
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget)
+    files = sorted(p.name for p in (tmp_path / "one").iterdir())
+    assert files == ["a.npy", "b.npy"]
+    assert sum((tmp_path / "one" / f).stat().st_size for f in files) <= budget
+    a1, a2 = np.load(tmp_path / "one" / "a.npy"), np.load(tmp_path / "two" / "a.npy")
+    assert a1.dtype == np.float32 and a1.ndim == 1 and 0 < a1.size < arrays["a"].size and (a1 == a2).all()
+    assert set(a1.tolist()) <= set(arrays["a"].reshape(-1).astype(np.float32).tolist())
+    b = np.load(tmp_path / "one" / "b.npy")  # fits its share: stored whole
+    assert b.shape == (11, 7) and (b == arrays["b"]).all()
 
 
 @pytest.mark.parametrize("nproc,preset,chain,chunks", [(3, None, "gaussian5,sobel", 0), (2, "ref-cpu", None, 0),

@@ -42,7 +42,7 @@ def _torchrun(n, args, tmp_path, timeout=300):
 def test_bench_gloo_gpu_processes(tmp_path, n):
     recs = _torchrun(n, [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--backend", "gloo-gpu",
                          "--width", "2048", "--height", "1536", "--steps", "6", "--warmup", "2",
-                         "--dist-steps", "2", "--ref-steps", "2", "--e2e-steps", "2"], tmp_path)
+                         "--full", "--dist-steps", "2", "--ref-steps", "2", "--e2e-steps", "2"], tmp_path)
     assert len(recs) == 1
     rec = recs[0]
     assert rec["n_gpus"] == n and rec["value"] > 0 and rec["verified_vs_golden"] is True

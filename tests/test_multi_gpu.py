@@ -41,7 +41,7 @@ def test_torchrun_bench_rccl(n, chain, depth):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(n), "--steps", "9", "--warmup", "2", "--width", "2048", "--height", "1024",
-           "--chain", chain, "--halo-depth", str(depth), "--dist-steps", "2", "--e2e-steps", "1"]
+           "--chain", chain, "--halo-depth", str(depth), "--full", "--dist-steps", "2", "--e2e-steps", "1"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -46,7 +46,8 @@ def _torchrun(args, tmp_path, timeout=420):
 
 def test_bench_host_8_processes(tmp_path):
     recs = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "9", "--warmup", "1",
-                      "--width", "96", "--height", "1600", "--backend", "host", "--dist-steps", "2"], tmp_path)
+                      "--width", "96", "--height", "1600", "--backend", "host", "--full", "--dist-steps", "2"],
+                     tmp_path)
     assert len(recs) == 1
     rec = recs[0]
     assert rec["n_gpus"] == N and rec["steps"] == 9 and rec["value"] > 0

@@ -199,7 +199,7 @@ def _bench(tmp_path, n, extra, env_extra, timeout=240):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(n), "--backend", "host", "--width", "96", "--height", "64", "--steps", "3", "--warmup", "1",
-           "--dist-steps", "2", *extra]
+           "--full", "--dist-steps", "2", *extra]
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1", **env_extra)
     t0 = time.time()
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=str(tmp_path))
