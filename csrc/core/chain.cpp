@@ -176,7 +176,9 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
       p.pro = pending;
       p.cmid = p.cout = c;
       std::string pro = prog_desc(pending);
-      p.desc = std::string(si.separable ? "separable " : "direct ") + si.name +
+      // rank filters (median / erode / dilate) are Direct passes: same halo,
+      // margin and launch contracts, their own kernel family (k_rank)
+      p.desc = std::string(si.rank != Rank::None ? "rank " : si.separable ? "separable " : "direct ") + si.name +
                (pro.empty() ? "" : " prologue[" + pro + "]") + " " + std::to_string(p.cin) +
                "->" + std::to_string(p.cout) + "ch border=" + border_name(p.border);
     }

@@ -10,6 +10,8 @@
 #include <thread>
 #include <vector>
 
+#include "stripe/rank_net.h"
+
 namespace stripe {
 
 int cpu_threads(int ranks_per_host) {
@@ -172,10 +174,69 @@ STRIPE_SIMD void finish_sobel(const int32_t* __restrict a, const int32_t* __rest
   }
 }
 
+// Rank filters: byte-wise min / max sweeps over whole extended rows.
+STRIPE_SIMD void min_into(uint8_t* __restrict d, const uint8_t* __restrict s, int n) {
+  for (int i = 0; i < n; ++i) d[i] = s[i] < d[i] ? s[i] : d[i];
+}
+STRIPE_SIMD void max_into(uint8_t* __restrict d, const uint8_t* __restrict s, int n) {
+  for (int i = 0; i < n; ++i) d[i] = s[i] > d[i] ? s[i] : d[i];
+}
+// compare-exchange: (a, b) <- (min, max), element by element
+STRIPE_SIMD void cex_u8(uint8_t* __restrict a, uint8_t* __restrict b, int n) {
+  for (int i = 0; i < n; ++i) {
+    const uint8_t lo = a[i] < b[i] ? a[i] : b[i], hi = a[i] < b[i] ? b[i] : a[i];
+    a[i] = lo;
+    b[i] = hi;
+  }
+}
+
+// One output row (E bytes) of a rank filter from the K extended ring rows
+// (EW bytes each, any order: the window's order statistics do not depend on it).
+// erode / dilate: vertical min / max of the rows, then horizontal min / max of
+// the K shifted views.  median: the columns of K are sorted by a network of
+// row-wide compare-exchanges (ranknet::ColSort), then ranknet::Select runs
+// over the K*K views (sorted column dx, element r) = sorted row r shifted by
+// dx pixels.  `work` holds K*EW + K*K*E bytes.
+template <int K>
+void rank_row(Rank rank, const uint8_t* const* rows, int C, int E, int EW, uint8_t* work, uint8_t* o) {
+  if (rank != Rank::Median) {
+    uint8_t* v = work;
+    std::memcpy(v, rows[0], (size_t)EW);
+    for (int dy = 1; dy < K; ++dy) (rank == Rank::Min ? min_into : max_into)(v, rows[dy], EW);
+    std::memcpy(o, v, (size_t)E);
+    for (int dx = 1; dx < K; ++dx) (rank == Rank::Min ? min_into : max_into)(o, v + (size_t)dx * C, E);
+    return;
+  }
+  uint8_t* col[K];
+  for (int r = 0; r < K; ++r) {
+    col[r] = work + (size_t)r * EW;
+    std::memcpy(col[r], rows[r], (size_t)EW);
+  }
+  using CS = ranknet::ColSort<K>;
+  for (int k = 0; k < CS::N; ++k) cex_u8(col[CS::at(k).i], col[CS::at(k).j], EW);
+  uint8_t* wire[K * K];
+  for (int dx = 0; dx < K; ++dx)
+    for (int r = 0; r < K; ++r) {
+      wire[dx * K + r] = work + (size_t)K * EW + (size_t)(dx * K + r) * E;
+      std::memcpy(wire[dx * K + r], col[r] + (size_t)dx * C, (size_t)E);
+    }
+  using SN = ranknet::Select<K>;
+  for (int k = 0; k < SN::N; ++k) {
+    const ranknet::Step s = SN::at(k);
+    if (s.mode == ranknet::kBoth) cex_u8(wire[s.i], wire[s.j], E);
+    else if (s.mode == ranknet::kMin) min_into(wire[s.i], wire[s.j], E);
+    else max_into(wire[s.j], wire[s.i], E);
+  }
+  std::memcpy(o, wire[SN::kOut], (size_t)E);
+}
+
 void stencil_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out, int W, RowGeom g, int ya, int yb) {
   const StencilInfo& si = stencil_info(p.sid);
   const int K = p.K, R = p.R, C = p.cmid;
   const int E = W * C, EW = (W + 2 * R) * C;
+  const bool rank = si.rank != Rank::None;
+  STRIPE_CHECK(!rank || K == 3 || K == 5, "rank filters come in sizes 3 and 5");
+  std::vector<uint8_t> rwork(rank ? (size_t)K * EW + (size_t)K * K * E : 0);
   std::vector<int> wy;
   if (si.sobel) {
     wy.resize((size_t)K * K);
@@ -198,44 +259,51 @@ void stencil_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out
     if (si.div == (1 << k)) sh = k;
 
   std::vector<uint8_t> ring((size_t)K * EW);
-  std::vector<int32_t> acc((size_t)E), acc2(si.sobel ? (size_t)E : 0);
+  std::vector<int32_t> acc(rank ? 0 : (size_t)E), acc2(si.sobel ? (size_t)E : 0);
   std::vector<uint16_t> vs(sep ? (size_t)EW : 0);
   std::vector<uint8_t> res((size_t)E);
   auto slot = [&](int y) { return ring.data() + (size_t)((y - (ya - R)) % K) * EW; };
   for (int y = ya - R; y < ya + R; ++y) ext_row(p, pt, in, W, g, y, slot(y));
   for (int y = ya; y < yb; ++y) {
     ext_row(p, pt, in, W, g, y + R, slot(y + R));
-    std::fill(acc.begin(), acc.end(), 0);
-    int32_t* a = acc.data();
-    if (sep) {
-      std::fill(vs.begin(), vs.end(), (uint16_t)0);
-      for (int dy = 0; dy < K; ++dy) tap_u8_u16(vs.data(), slot(y + dy - R), si.w1[(size_t)dy], EW);
-      for (int dx = 0; dx < K; ++dx) tap_u16(a, vs.data() + (size_t)dx * C, si.w1[(size_t)dx], E);
+    uint8_t* o = res.data();
+    if (rank) {
+      const uint8_t* rows[5];
+      for (int dy = 0; dy < K; ++dy) rows[dy] = slot(y + dy - R);
+      if (K == 3) rank_row<3>(si.rank, rows, C, E, EW, rwork.data(), o);
+      else rank_row<5>(si.rank, rows, C, E, EW, rwork.data(), o);
     } else {
-      if (si.sobel) std::fill(acc2.begin(), acc2.end(), 0);
-      for (int dy = 0; dy < K; ++dy) {
-        const uint8_t* r = slot(y + dy - R);
-        for (int dx = 0; dx < K; ++dx) {
-          const uint8_t* s = r + (size_t)dx * C;
-          const int w = si.w[(size_t)dy * K + dx];
-          if (w != 0) tap_u8(a, s, w, E);
-          if (si.sobel && wy[(size_t)dy * K + dx] != 0) tap_u8(acc2.data(), s, wy[(size_t)dy * K + dx], E);
+      std::fill(acc.begin(), acc.end(), 0);
+      int32_t* a = acc.data();
+      if (sep) {
+        std::fill(vs.begin(), vs.end(), (uint16_t)0);
+        for (int dy = 0; dy < K; ++dy) tap_u8_u16(vs.data(), slot(y + dy - R), si.w1[(size_t)dy], EW);
+        for (int dx = 0; dx < K; ++dx) tap_u16(a, vs.data() + (size_t)dx * C, si.w1[(size_t)dx], E);
+      } else {
+        if (si.sobel) std::fill(acc2.begin(), acc2.end(), 0);
+        for (int dy = 0; dy < K; ++dy) {
+          const uint8_t* r = slot(y + dy - R);
+          for (int dx = 0; dx < K; ++dx) {
+            const uint8_t* s = r + (size_t)dx * C;
+            const int w = si.w[(size_t)dy * K + dx];
+            if (w != 0) tap_u8(a, s, w, E);
+            if (si.sobel && wy[(size_t)dy * K + dx] != 0) tap_u8(acc2.data(), s, wy[(size_t)dy * K + dx], E);
+          }
         }
       }
-    }
-    uint8_t* o = res.data();
-    const int32_t* a2 = acc2.data();
-    if (si.sobel && si.l2) {
-      for (int i = 0; i < E; ++i) o[i] = sat(isqrt_round(a[i] * a[i] + a2[i] * a2[i]));
-    } else if (si.sobel) {
-      finish_sobel(a, a2, o, E);
-    } else if (si.div > 1 && sh >= 0) {
-      finish_shift(a, o, si.div / 2, sh, E);
-    } else if (si.div > 1) {
-      const int d = si.div, h = si.div / 2;  // sums >= 0 for the smoothing filters
-      for (int i = 0; i < E; ++i) o[i] = sat((a[i] + h) / d);
-    } else {
-      finish_sat(a, o, E);
+      const int32_t* a2 = acc2.data();
+      if (si.sobel && si.l2) {
+        for (int i = 0; i < E; ++i) o[i] = sat(isqrt_round(a[i] * a[i] + a2[i] * a2[i]));
+      } else if (si.sobel) {
+        finish_sobel(a, a2, o, E);
+      } else if (si.div > 1 && sh >= 0) {
+        finish_shift(a, o, si.div / 2, sh, E);
+      } else if (si.div > 1) {
+        const int d = si.div, h = si.div / 2;  // sums >= 0 for the smoothing filters
+        for (int i = 0; i < E; ++i) o[i] = sat((a[i] + h) / d);
+      } else {
+        finish_sat(a, o, E);
+      }
     }
     if (p.border == Border::Skip) {  // golden.cpp:133 (the reference's interior-only bounds)
       const int gy = g.row0 + y;

@@ -52,6 +52,20 @@ StencilInfo make_sep(StencilId id, const char* name) {
   return s;
 }
 
+template <class F>
+StencilInfo make_rank(StencilId id, const char* name) {
+  static_assert(!F::SEP && !F::SOBEL && F::DIV == 1 && F::RANK != 0, "rank filter definition");
+  StencilInfo s;
+  s.id = id;
+  s.name = name;
+  s.K = F::K;
+  s.separable = false;
+  s.sobel = false;
+  s.div = 1;
+  s.rank = (Rank)F::RANK;
+  return s;
+}
+
 const std::vector<StencilInfo>& table() {
   static const std::vector<StencilInfo> t = [] {
     std::vector<StencilInfo> v((size_t)StencilId::kCount);
@@ -66,6 +80,12 @@ const std::vector<StencilInfo>& table() {
     v[(int)StencilId::Laplace] = make_info<sdef::Laplace>(StencilId::Laplace, "laplace");
     v[(int)StencilId::Sobel] = make_info<sdef::Sobel>(StencilId::Sobel, "sobel");
     v[(int)StencilId::SobelL2] = make_info<sdef::SobelL2>(StencilId::SobelL2, "sobel_l2");
+    v[(int)StencilId::Median3] = make_rank<sdef::Median3>(StencilId::Median3, "median3");
+    v[(int)StencilId::Median5] = make_rank<sdef::Median5>(StencilId::Median5, "median5");
+    v[(int)StencilId::Erode3] = make_rank<sdef::Erode3>(StencilId::Erode3, "erode3");
+    v[(int)StencilId::Erode5] = make_rank<sdef::Erode5>(StencilId::Erode5, "erode5");
+    v[(int)StencilId::Dilate3] = make_rank<sdef::Dilate3>(StencilId::Dilate3, "dilate3");
+    v[(int)StencilId::Dilate5] = make_rank<sdef::Dilate5>(StencilId::Dilate5, "dilate5");
     return v;
   }();
   return t;
@@ -118,11 +138,26 @@ bool stencil_from_name(const std::string& name, StencilId* out) {
       {"laplacian", StencilId::Laplace}, {"sobel", StencilId::Sobel},
       {"edge", StencilId::Sobel},        {"sobel_l2", StencilId::SobelL2},
       {"magnitude", StencilId::SobelL2},
+      {"median", StencilId::Median3},    {"median3", StencilId::Median3},
+      {"median5", StencilId::Median5},   {"erode", StencilId::Erode3},
+      {"erode3", StencilId::Erode3},     {"erode5", StencilId::Erode5},
+      {"dilate", StencilId::Dilate3},    {"dilate3", StencilId::Dilate3},
+      {"dilate5", StencilId::Dilate5},
   };
   auto it = alias.find(name);
   if (it == alias.end()) return false;
   *out = it->second;
   return true;
+}
+
+const char* rank_name(Rank r) {
+  switch (r) {
+    case Rank::None: return "none";
+    case Rank::Min: return "min";
+    case Rank::Max: return "max";
+    case Rank::Median: return "median";
+  }
+  return "?";
 }
 
 int Op::radius() const {
@@ -205,6 +240,26 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
     auto parts = split(tok, ':');
     const std::string name = parts[0];
     StencilId sid;
+    // rank filters come in sizes 3 and 5 only: say so, rather than "unknown filter"
+    for (const char* fam : {"median", "erode", "dilate", "open", "close"}) {
+      const std::string f = fam;
+      if (name.compare(0, f.size(), f) != 0) continue;
+      const std::string sz = name.substr(f.size());
+      const bool sugar = f == "open" || f == "close";
+      STRIPE_CHECK(sz == "3" || sz == "5" || (sz.empty() && !sugar),
+                   "'" << name << "': " << f << " takes a window size of 3 or 5 (" << f << "3, " << f << "5)");
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << f << " takes no arguments");
+    }
+    if (name == "open3" || name == "open5" || name == "close3" || name == "close5") {
+      // morphological opening = erode then dilate, closing = dilate then erode;
+      // an @border suffix applies to both ops
+      const std::string k(1, name.back());
+      const std::string suffix = op.has_border ? std::string("@") + border_name(op.border) : "";
+      const bool open = name[0] == 'o';
+      auto sub = parse_chain((open ? "erode" : "dilate") + k + suffix + "," + (open ? "dilate" : "erode") + k + suffix);
+      ops.insert(ops.end(), sub.begin(), sub.end());
+      continue;
+    }
     if (name == "gray" || name == "grayscale" || name == "grey") {
       op.kind = OpKind::Gray;
       op.gray = GrayMode::BT601;
@@ -290,7 +345,8 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
     } else {
       fail("unknown filter '" + name +
            "' (gray[:ref|bt601], contrast:F[:cv], invert, brightness:D, threshold:T, expand, "
-           "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb])");
+           "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
+           "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb])");
     }
     if (op.has_border) op.text += std::string("@") + border_name(op.border);
     ops.push_back(op);

@@ -4,12 +4,15 @@
 // ref-cpu preset / host backend (the reference's OpenCV chain, kern.cpp:58-77).
 #include "stripe/golden.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
 namespace stripe {
 
 namespace {
+
+constexpr int kMaxRank = 5;  // largest rank-filter window (median5 / erode5 / dilate5)
 
 inline uint8_t sat(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
@@ -116,6 +119,7 @@ void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int
     return;
   }
   const StencilInfo& si = stencil_info(p.sid);
+  STRIPE_CHECK(si.rank == Rank::None || K <= kMaxRank, "rank window too large");
   std::vector<int> wy;  // sobel's second kernel (transpose of Gx)
   if (si.sobel) {
     wy.resize((size_t)K * K);
@@ -136,6 +140,23 @@ void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int
         int v;
         if (skip) {
           v = rc.at(y, x)[c];
+        } else if (si.rank != Rank::None) {
+          // rank filters: order statistics of the K*K window values (border
+          // pixels are members like any other)
+          uint8_t win[kMaxRank * kMaxRank];
+          int n = 0;
+          for (int dy = 0; dy < K; ++dy) {
+            const uint8_t* r = rc.at(y + dy - R, x - R) + c;
+            for (int dx = 0; dx < K; ++dx) win[n++] = r[(size_t)dx * C];
+          }
+          if (si.rank == Rank::Min) {
+            v = *std::min_element(win, win + n);
+          } else if (si.rank == Rank::Max) {
+            v = *std::max_element(win, win + n);
+          } else {
+            std::nth_element(win, win + n / 2, win + n);
+            v = win[n / 2];
+          }
         } else {
           int s = 0, s2 = 0;
           for (int dy = 0; dy < K; ++dy) {

@@ -202,6 +202,12 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
     case StencilId::Gaussian7: dev::launch_filter<Gaussian7>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
     case StencilId::Box3: dev::launch_filter<Box3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
     case StencilId::Box5: dev::launch_filter<Box5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Median3: dev::launch_filter<Median3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Median5: dev::launch_filter<Median5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Erode3: dev::launch_filter<Erode3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Erode5: dev::launch_filter<Erode5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Dilate3: dev::launch_filter<Dilate3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+    case StencilId::Dilate5: dev::launch_filter<Dilate5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
     default: fail("unknown stencil");
   }
   HIP_CHECK(hipGetLastError());

@@ -37,6 +37,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 namespace stripe {
 namespace dev {
@@ -1168,6 +1169,20 @@ inline int stencil_cap(bool nt, int wgs, int family_default) {
   return nt ? family_default : 0;
 }
 
+// Rank filters (sdef::RankDef: median / erode / dilate) have their own kernel
+// family, k_rank; launch_rank is defined in rank_kernels.h, which the unit
+// that instantiates those filters includes (stencil_inst_e.hip).
+template <class F, class = void>
+struct RankTag {
+  static constexpr int value = 0;
+};
+template <class F>
+struct RankTag<F, std::void_t<decltype(F::RANK)>> {
+  static constexpr int value = F::RANK;
+};
+template <int C, class F, int PRO, bool EXP>
+void launch_rank(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s);
+
 template <int C, class F, int PRO, bool EXP = false>
 void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s,
                 int order = 0) {
@@ -1224,7 +1239,9 @@ void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1,
       }
     }
   }
-  if constexpr (F::SEP) {
+  if constexpr (RankTag<F>::value != 0) {
+    launch_rank<C, F, PRO, EXP>(skip, nt, wgs, a, tiles, n0, n1, band, s);
+  } else if constexpr (F::SEP) {
     const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP>, k_sep<C, F, PRO, false, kNtAux, EXP>,
                       k_sep<C, F, PRO, true, 0, EXP>, k_sep<C, F, PRO, true, kNtAux, EXP>};
     const K fn = fns[2 * skip + nt];
@@ -1274,7 +1291,7 @@ void launch_filter(const Pass& p, const KArgs& a, int tiles, int n0, int n1, int
 #define STRIPE_INSTANTIATE_LAUNCH_FILTER(F) template STRIPE_LAUNCH_FILTER_SIG(F);
 #define STRIPE_STENCIL_FILTERS(X) \
   X(Emboss3) X(Emboss5) X(Sharpen) X(Laplace) X(Sobel) X(SobelL2) X(Gaussian3) X(Gaussian5) X(Gaussian7) X(Box3) \
-  X(Box5)
+  X(Box5) X(Median3) X(Median5) X(Erode3) X(Erode5) X(Dilate3) X(Dilate5)
 
 }  // namespace dev
 }  // namespace stripe

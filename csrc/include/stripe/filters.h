@@ -10,6 +10,11 @@
 //   emboss3/5     kernel.cu:64-94, kern.cpp:62-75
 // North-star filters (BASELINE.json): invert, brightness, gaussian, sobel, sharpen,
 // large-kernel blur.  Extras: gaussian3/7, box3/5, laplace, threshold, expand.
+// Rank filters: median3/5, erode3/5, dilate3/5 over the square K x K window of
+// the border-extended image (border pixels are window members like any other:
+// with @constant the zeros outside the frame take part, so erode3@constant
+// darkens the frame edge - unlike OpenCV's morphology default, which ignores
+// them); open3/5 = erode,dilate and close3/5 = dilate,erode are parser sugar.
 #pragma once
 
 #include <string>
@@ -45,8 +50,20 @@ enum class StencilId : int {
   Laplace,
   Sobel,
   SobelL2,
+  Median3,
+  Median5,
+  Erode3,
+  Erode5,
+  Dilate3,
+  Dilate5,
   kCount
 };
+
+// Rank (order-statistic) filters over the K x K window: no weights, the output
+// is the minimum (erode), maximum (dilate) or the element K*K/2 of the sorted
+// window (median).
+enum class Rank : int { None = 0, Min, Max, Median };
+const char* rank_name(Rank r);
 
 struct StencilInfo {
   StencilId id;
@@ -58,6 +75,7 @@ struct StencilInfo {
   int div;               // out = sat(floor((sum + div/2) / div)) (div==1: sat(sum))
   std::vector<int> w;    // K*K row-major [dy][dx] (correlation, like filter2D)
   std::vector<int> w1;   // separable 1-D taps
+  Rank rank = Rank::None;  // rank filter: w / w1 empty, div 1
 };
 
 const StencilInfo& stencil_info(StencilId id);

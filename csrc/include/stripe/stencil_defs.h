@@ -136,5 +136,24 @@ struct Box5 {
   STRIPE_HD static constexpr int w(int, int) { return 1; }
 };
 
+// Rank filters (erode = window minimum, dilate = maximum, median = element
+// K*K/2 of the sorted window): no weights, a compile-time rank tag instead.
+// The tags mirror stripe::Rank (filters.h).
+constexpr int kRankMin = 1, kRankMax = 2, kRankMedian = 3;
+
+template <int K_, int RANK_>
+struct RankDef {
+  static constexpr bool BINOM = false;
+  static constexpr int K = K_, R = K_ / 2, DIV = 1;
+  static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int RANK = RANK_;
+};
+struct Median3 : RankDef<3, kRankMedian> {};
+struct Median5 : RankDef<5, kRankMedian> {};
+struct Erode3 : RankDef<3, kRankMin> {};
+struct Erode5 : RankDef<5, kRankMin> {};
+struct Dilate3 : RankDef<3, kRankMax> {};
+struct Dilate5 : RankDef<5, kRankMax> {};
+
 }  // namespace sdef
 }  // namespace stripe

@@ -21,6 +21,7 @@
 #include "stripe/cpu_exec.h"
 #include "stripe/image.h"
 #include "stripe/partition.h"
+#include "stripe/rank_net.h"
 
 namespace py = pybind11;
 using namespace stripe;
@@ -161,8 +162,30 @@ PYBIND11_MODULE(_C, m) {
     d["div"] = s.div;
     d["separable"] = s.separable;
     d["sobel"] = s.sobel;
+    d["rank"] = rank_name(s.rank);  // "none" | "min" | "max" | "median" (rank filters: w empty)
     return d;
   });
+  m.def("rank_network", [](int K) {
+    // the median networks of rank_net.h as (i, j, mode) steps, for the tests
+    STRIPE_CHECK(K == 3 || K == 5, "rank networks exist for K = 3 and 5");
+    py::dict d;
+    py::list cs, sel;
+    auto fill = [](py::list& l, auto net) {
+      for (int k = 0; k < decltype(net)::N; ++k) l.append(py::make_tuple(net.at(k).i, net.at(k).j, net.at(k).mode));
+    };
+    if (K == 3) {
+      fill(cs, ranknet::ColSort<3>{});
+      fill(sel, ranknet::Select<3>{});
+      d["out"] = ranknet::Select<3>::kOut;
+    } else {
+      fill(cs, ranknet::ColSort<5>{});
+      fill(sel, ranknet::Select<5>{});
+      d["out"] = ranknet::Select<5>::kOut;
+    }
+    d["colsort"] = cs;
+    d["select"] = sel;
+    return d;
+  }, "compare-exchange networks of the KxK median (mode 0: both, 1: min -> i, 2: max -> j)");
   m.def("gaussian_1d", &gaussian_1d, py::arg("K"), py::arg("sigma") = 0.0);
   m.def("describe_chain", [](const std::string& chain, int cin, const std::string& border, bool fuse) {
     return compile_chain(parse_chain(chain), cin, parse_border(border), fuse).describe();

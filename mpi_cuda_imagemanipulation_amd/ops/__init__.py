@@ -43,6 +43,12 @@ FILTERS = {
     "laplace": "[[0,1,0],[1,-4,1],[0,1,0]]",
     "sobel": "sat(|Gx| + |Gy|)",
     "sobel_l2 / magnitude": "sat(round(sqrt(Gx^2 + Gy^2))), exact integer rounding",
+    "median3 / median5 (median)": "element K*K/2 of the sorted KxK window, per channel",
+    "erode3 / erode5 (erode)": "minimum of the KxK window; border pixels are window members "
+                               "(@constant: the zeros outside the frame darken its edge)",
+    "dilate3 / dilate5 (dilate)": "maximum of the KxK window",
+    "open3 / open5": "erodeK,dilateK (an @border suffix applies to both)",
+    "close3 / close5": "dilateK,erodeK",
     "blur:K[:sigma][:lsb]": "KxK float Gaussian (separable MFMA path), K <= 33; :lsb = every output within 1 LSB, "
                             "2.5x fewer MFMAs",
     "conv:K:w0;w1;...[:lsb]": "generic KxK float correlation (MFMA path); :lsb = within 1 LSB, 2/3 of the MFMAs",
@@ -189,6 +195,26 @@ def emboss(x, size: int = 3, border: str = "reflect101"):
     return apply(x, f"emboss{size}", border)
 
 
+def median(x, k: int = 3, border: str = "reflect101"):
+    return apply(x, f"median{int(k)}", border)
+
+
+def erode(x, k: int = 3, border: str = "reflect101"):
+    return apply(x, f"erode{int(k)}", border)
+
+
+def dilate(x, k: int = 3, border: str = "reflect101"):
+    return apply(x, f"dilate{int(k)}", border)
+
+
+def morph_open(x, k: int = 3, border: str = "reflect101"):
+    return apply(x, f"open{int(k)}", border)
+
+
+def morph_close(x, k: int = 3, border: str = "reflect101"):
+    return apply(x, f"close{int(k)}", border)
+
+
 def conv2d(x, weights, border: str = "reflect101"):
     """Generic KxK float correlation on the MFMA path (weights: KxK array)."""
     w = np.asarray(weights, dtype=np.float64)
@@ -222,5 +248,6 @@ def clear_cache() -> None:
 
 __all__ = [
     "FILTERS", "apply", "reference", "grayscale", "contrast", "invert", "brightness", "threshold",
-    "gaussian_blur", "box_blur", "sobel", "sharpen", "laplace", "emboss", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
+    "gaussian_blur", "box_blur", "sobel", "sharpen", "laplace", "emboss",
+    "median", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
 ]
