@@ -152,7 +152,13 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     p.border = op.has_border ? op.border : default_border;
     normalize(pending);
     const bool conv = op.kind == OpKind::Conv;
-    if (conv || !fuse || !pending.prologue_ok()) flush_pointwise();
+    // a constant border is zero AFTER the prologue (golden.cpp build_cache), but
+    // a fused prologue cooks the raw zeros of the margins and of the rows
+    // outside the frame: a program that moves the zero pixel (gray maps zero to
+    // zero, so that is post[0] != 0) runs as a pass of its own, which zeroes
+    // its constant margins, and the stencil reads raw zeros
+    const bool moves_zero = p.border == Border::Constant && pending.has_post && pending.post[0] != 0;
+    if (conv || !fuse || !pending.prologue_ok() || moves_zero) flush_pointwise();
     if (conv) {
       STRIPE_CHECK(p.border != Border::Skip, "skip border is only defined for integer stencils");
       p.kind = PassKind::Conv;

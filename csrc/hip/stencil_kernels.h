@@ -1222,7 +1222,8 @@ void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1,
         const char* e = std::getenv("STRIPE_SOBEL_WIDE");
         return !(e && std::atoi(e) == 0);
       }();
-      if (rp && !skip) {
+      // k_sobel_rp stores its sums as they are: an epilogue LUT takes the k_sep form
+      if (rp && !skip && !a.has_epi) {
         const int pb = pb_env >= 0 ? pb_env : (band == 8 ? 8 : 0);
         const K fns[2][3][2] = {{{k_sobel_rp<0>, k_sobel_rp<kNtAux>},
                                  {k_sobel_rp<0, 8>, k_sobel_rp<kNtAux, 8>},
