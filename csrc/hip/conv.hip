@@ -638,7 +638,9 @@ static int conv_shift(const std::vector<float>& w, int ND) {
 }
 
 // Largest output error (in LSB) of ND-digit weights: |x - 128| <= 128 times
-// the summed quantisation residuals (the digit sums themselves are exact).
+// the summed quantisation residuals (the digit sums themselves are exact, and
+// the shift back, conv_bias, is built from the exact weights: only the centred
+// sum carries the residuals).
 static double conv_quant_bound(const std::vector<float>& w, int ND) {
   const int S = conv_shift(w, ND);
   double r = 0;
@@ -663,11 +665,11 @@ static void prepare_conv_i8(const Pass& p, PassConsts* pc, hipStream_t s) {
   const int64_t wmax = ND == 3 ? (1 << 23) - (1 << 15) : (1 << 15) - (1 << 7);
   const int S = conv_shift(p.conv_w, ND);
   std::vector<int64_t> W((size_t)K * K);
-  int64_t wsum = 0;
+  double wsum = 0;  // of the exact f32 weights, as prepare_sep_consts does for the blur
   for (size_t i = 0; i < W.size(); ++i) {
     W[i] = std::llround(std::ldexp((double)p.conv_w[i], S));
     STRIPE_CHECK(std::llabs(W[i]) <= wmax, "weight digit range");
-    wsum += W[i];
+    wsum += (double)p.conv_w[i];
   }
   auto digit = [](int64_t w, int d) {
     int64_t v = w;
@@ -698,7 +700,9 @@ static void prepare_conv_i8(const Pass& p, PassConsts* pc, hipStream_t s) {
                  "digits");
   pc->conv_mode = ND == 3 ? 1 : 2;
   pc->conv_scale = std::ldexp(1.0, -S);
-  pc->conv_bias = 128.0 * (double)wsum * pc->conv_scale;
+  // sum (x - 128) Wq 2^-S + 128 sum w = sum x w - sum (x - 128) r 2^-S: a bias of
+  // 128 sum Wq 2^-S would leave sum x r 2^-S, up to 255 / 128 of the bound
+  pc->conv_bias = 128.0 * wsum;
   pc->conv_bytes = host.size();
   HIP_CHECK(hipMalloc(&pc->conv, pc->conv_bytes));
   HIP_CHECK(hipMemcpyAsync(pc->conv, host.data(), pc->conv_bytes, hipMemcpyHostToDevice, s));

@@ -47,17 +47,18 @@ def torch_sums(img: np.ndarray, w: np.ndarray, border: str, device: str = "cpu")
     R = K // 2
     mode = {"reflect101": "reflect", "constant": "constant", "replicate": "replicate"}[border]
     wt = torch.from_numpy(np.ascontiguousarray(w)).to(device=device, dtype=torch.float64).view(1, 1, K, K)
-    out = []
-    for p in _planes(img):
-        x = torch.from_numpy(np.ascontiguousarray(p)).to(device=device).view(1, 1, *p.shape)
-        H, W = p.shape
-        if border == "reflect101" and (H <= R or W <= R):
-            # torch's reflect pad needs pad < size: pad in steps (reflect101 is periodic)
-            x = _reflect101_pad(x, R)
-        else:
-            x = F.pad(x, (R, R, R, R), mode=mode)
-        out.append(F.conv2d(x, wt).view(H, W).cpu().numpy())  # conv2d is a correlation
-    return _stack(out, img)
+    # the planes go through one conv2d call as a batch (any number of them: a
+    # stack of frames can be passed as HxWxN)
+    planes = _planes(img)
+    H, W = planes[0].shape
+    x = torch.from_numpy(np.ascontiguousarray(np.stack(planes))).to(device=device).view(len(planes), 1, H, W)
+    if border == "reflect101" and (H <= R or W <= R):
+        # torch's reflect pad needs pad < size: pad in steps (reflect101 is periodic)
+        x = _reflect101_pad(x, R)
+    else:
+        x = F.pad(x, (R, R, R, R), mode=mode)
+    out = F.conv2d(x, wt).view(len(planes), H, W).cpu().numpy()  # conv2d is a correlation
+    return _stack(list(out), img)
 
 
 def _reflect101_pad(x, R):

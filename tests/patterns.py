@@ -61,12 +61,13 @@ def _half_tb(H, W, phase):
     return img if phase % 2 == 0 else 255 - img
 
 
-def impulse_sites(H, W, C):
+def impulse_sites(H, W, C, seams=SEAMS):
     """(y, x, channel) of the impulses: corners, centre, and the pixel holding
-    the last byte before / the first byte after every seam inside the row."""
+    the last byte before / the first byte after every seam inside the row
+    (`seams`: the seam periods in bytes)."""
     sites = [(H // 2, W // 2, 0), (0, 0, 1), (0, W - 1, 2), (H - 1, 0, 2), (H - 1, W - 1, 1)]
     k = 0
-    for period in SEAMS:
+    for period in seams:
         for s in range(period, W * C, period):
             y = (3 + 4 * k) % H
             k += 1
@@ -97,7 +98,7 @@ def _three(fn, H, W, shift):
     return np.stack([fn(H, W, c if shift else 0) for c in range(3)], axis=-1)
 
 
-def patterns(H, W, C, seed=7):
+def patterns(H, W, C, seed=7, seams=SEAMS):
     assert C in (1, 3)
     rng = np.random.default_rng(seed)
     variants = (("", False),) if C == 1 else (("/same", False), ("/shift", True))
@@ -119,7 +120,7 @@ def patterns(H, W, C, seed=7):
         else:
             yield f"extremes{tag}", np.repeat(rng.choice(EXTREMES, size=(H, W))[..., None], 3, axis=-1)
         for bg, fg, name in ((0, 255, "impulse255on0"), (255, 0, "impulse0on255")):
-            for n, frame in enumerate(_pack(impulse_sites(H, W, C))):
+            for n, frame in enumerate(_pack(impulse_sites(H, W, C, seams))):
                 img = np.full((H, W) if C == 1 else (H, W, 3), bg, np.uint8)
                 for y, x, c in frame:
                     if C == 1:
