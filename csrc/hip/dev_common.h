@@ -80,17 +80,6 @@ __device__ __forceinline__ int border_index_dev(int i, int n, int b) {
   return j < n ? j : period - j;
 }
 
-// Input row pointer for local row y with the global-edge border applied (scalar).
-__device__ __forceinline__ const uint8_t* in_row(const KArgs& a, int y) {
-  int g = a.row0 + y;
-  if (g < 0 || g >= a.Hg) {
-    const int m = border_index_dev(g, a.Hg, a.border);
-    if (m < 0) return a.zero_row;
-    g = m;
-  }
-  return a.in + (int64_t)(g - a.row0) * a.in_pitch;
-}
-
 // Byte offset (in the input allocation) of local row y's origin, global-edge
 // border applied (scalar; no memory access).
 __device__ __forceinline__ uint32_t in_row_off(const KArgs& a, int y) {
@@ -143,10 +132,6 @@ __device__ __forceinline__ void band_range(const KArgs& a, int by, int& ys, int&
   }
 }
 
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&d)[4], int j) {
-  return (d[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
-}
-
 __device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   return a | (b << 8) | (c << 16) | (d << 24);
 }
@@ -183,25 +168,6 @@ __device__ __forceinline__ void lut16(const uint8_t* lut, uint32_t (&o)[4]) {
     const uint32_t w = o[q];
     o[q] = pack4(lut[w & 0xFF], lut[(w >> 8) & 0xFF], lut[(w >> 16) & 0xFF], lut[w >> 24]);
   }
-}
-
-// Store 16 output bytes at row + cb; only bytes < E (straddling chunk is split).
-// Static byte indices only (a dynamic index would put `o` in scratch).
-__device__ __forceinline__ void store_chunk(uint8_t* row, int cb, int E, const uint32_t (&o)[4]) {
-  if (cb + 16 <= E) {
-    *reinterpret_cast<uint4*>(row + cb) = make_uint4(o[0], o[1], o[2], o[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (cb + j < E) row[cb + j] = (uint8_t)byte_of(o, j);
-  }
-}
-
-// True for lanes whose chunk needs the cold path (straddles E or feeds margins).
-template <int C>
-__device__ __forceinline__ bool edge_lane(int cb, int E, int px) {
-  const int reach = (px + 1) * C;
-  return cb + 16 > E || (px > 0 && (cb < reach || cb + 16 > E - reach));
 }
 
 }  // namespace dev

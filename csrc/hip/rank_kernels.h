@@ -2,14 +2,11 @@
 // template; instantiated in stencil_inst_e.hip.
 #pragma once
 
-// Same wave tile as k_direct (stencil_kernels.h): one wave = 64 lanes x 16
-// bytes, 62 output chunks and a halo chunk each side, a K-row register ring of
-// prologue-applied rows as packed u16 pairs, extended by the neighbour lanes'
-// edge dwords (DPP wave shifts), the y loop unrolled K times with the next K
-// raw rows in flight, raw buffer loads / stores with kOOB lane masking, no
-// workgroup barrier and no LDS in the row loop.  It reads WaveTask / KArgs the
-// same way, so bands, the two output ranges and re-based launches need nothing
-// special.
+// k_rank is the register-ring row walk of k_direct as a device function (ring_task,
+// stencil_kernels.h: wave tile, K-row ring of prologue-applied rows as packed
+// u16 pairs extended by the neighbour lanes' edge dwords, K rows in flight,
+// @skip merge, epilogue, stores and margins) with RankRow as its row operation,
+// so bands, the two output ranges and re-based launches need nothing special.
 //
 // The arithmetic is packed u16 min / max (v_pk_min_u16 / v_pk_max_u16: one
 // VALU instruction per two pixels) on the pairs the ring already holds:
@@ -59,137 +56,81 @@ __device__ __forceinline__ void run_net(uint32_t (&w)[NW]) {
   run_net<Net>(w, std::make_index_sequence<Net::N>{});
 }
 
-// The lane's 8 output pairs of one row from the K extended ring rows.
-template <int C, class F, int NX, int NE>
-__device__ __forceinline__ void rank_row(const uint32_t (&ring)[F::K][NE], uint32_t (&h)[8]) {
-  constexpr int K = F::K, R = F::R;
-  // u16 index of the window's view dx for output pair pp (as k_direct's taps)
-  auto view = [](int pp, int dx) __attribute__((always_inline)) { return 2 * NX + 2 * pp + (dx - R) * C; };
-  if constexpr (F::RANK == sdef::kRankMedian) {
-    uint32_t s[K][NE];  // s[r]: element r (ascending) of every column
+// Row operation of the rank filters: the lane's 8 output pairs of one row from
+// the K extended ring rows (the unrolled step o is not needed, see above).
+template <int C, class F>
+struct RankRow {
+  static constexpr int NX = RingDims<C, F>::NX, NE = RingDims<C, F>::NE;
+  __device__ __forceinline__ void operator()(const uint32_t (&ring)[F::K][NE], int, uint32_t (&h)[8]) const {
+    constexpr int K = F::K, R = F::R;
+    // u16 index of the window's view dx for output pair pp (as k_direct's taps)
+    auto view = [](int pp, int dx) __attribute__((always_inline)) { return 2 * NX + 2 * pp + (dx - R) * C; };
+    if constexpr (F::RANK == sdef::kRankMedian) {
+      uint32_t s[K][NE];  // s[r]: element r (ascending) of every column
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
-      uint32_t col[K];
+      for (int e = 0; e < NE; ++e) {
+        uint32_t col[K];
 #pragma unroll
-      for (int r = 0; r < K; ++r) col[r] = ring[r][e];
-      run_net<ranknet::ColSort<K>>(col);
+        for (int r = 0; r < K; ++r) col[r] = ring[r][e];
+        run_net<ranknet::ColSort<K>>(col);
 #pragma unroll
-      for (int r = 0; r < K; ++r) s[r][e] = col[r];
-    }
+        for (int r = 0; r < K; ++r) s[r][e] = col[r];
+      }
 #pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {  // one output pair at a time: K*K live wires
-      uint32_t w[K * K];
+      for (int pp = 0; pp < 8; ++pp) {  // one output pair at a time: K*K live wires
+        uint32_t w[K * K];
 #pragma unroll
-      for (int dx = 0; dx < K; ++dx)
+        for (int dx = 0; dx < K; ++dx)
 #pragma unroll
-        for (int r = 0; r < K; ++r) w[dx * K + r] = pair_at(s[r], view(pp, dx));
-      run_net<ranknet::Select<K>>(w);
-      h[pp] = w[ranknet::Select<K>::kOut];
-    }
-  } else {
-    constexpr bool kMin = F::RANK == sdef::kRankMin;
-    uint32_t v[NE];
+          for (int r = 0; r < K; ++r) w[dx * K + r] = pair_at(s[r], view(pp, dx));
+        run_net<ranknet::Select<K>>(w);
+        h[pp] = w[ranknet::Select<K>::kOut];
+      }
+    } else {
+      constexpr bool kMin = F::RANK == sdef::kRankMin;
+      uint32_t v[NE];
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
-      uint32_t m = ring[0][e];
+      for (int e = 0; e < NE; ++e) {
+        uint32_t m = ring[0][e];
 #pragma unroll
-      for (int r = 1; r < K; ++r) m = kMin ? pk_min_u16(m, ring[r][e]) : pk_max_u16(m, ring[r][e]);
-      v[e] = m;
-    }
+        for (int r = 1; r < K; ++r) m = kMin ? pk_min_u16(m, ring[r][e]) : pk_max_u16(m, ring[r][e]);
+        v[e] = m;
+      }
 #pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-      uint32_t m = pair_at(v, view(pp, 0));
+      for (int pp = 0; pp < 8; ++pp) {
+        uint32_t m = pair_at(v, view(pp, 0));
 #pragma unroll
-      for (int dx = 1; dx < K; ++dx)
-        m = kMin ? pk_min_u16(m, pair_at(v, view(pp, dx))) : pk_max_u16(m, pair_at(v, view(pp, dx)));
-      h[pp] = m;
+        for (int dx = 1; dx < K; ++dx)
+          m = kMin ? pk_min_u16(m, pair_at(v, view(pp, dx))) : pk_max_u16(m, pair_at(v, view(pp, dx)));
+        h[pp] = m;
+      }
     }
   }
-}
+};
 
 // K = 5: the sorted columns (K * NE dwords) live beside the ring and the K raw
 // rows in flight; 2 waves per SIMD (256 VGPRs) rather than a scratch spill.
 template <int C, class F, int PRO, bool SKIP, int SAUX, bool EXP = false>
 __global__ __launch_bounds__(kNT, (F::K >= 5 ? 2 : 4)) void k_rank(KArgs a) {
-  static_assert(!EXP || C == 1, "expand epilogue needs a 1-channel stencil");
   static_assert(F::RANK != 0, "k_rank runs rank filters");
-  constexpr int R = F::R, K = F::K;
-  constexpr int NX = (R * C + 1) / 2;  // neighbour dwords per side
-  constexpr int NE = 8 + 2 * NX;       // extended row dwords
-  constexpr int CIN = is_gray(PRO) ? 3 : 1;
   __shared__ uint8_t luts[768];
+  __shared__ __attribute__((aligned(16))) uint4 xbuf[EXP ? kWaves : 1][EXP ? 3 * kW : 1];
   if (PRO != PRO_NONE || a.has_epi) {
-    load_luts<PRO>(a, luts);
+    load_luts(a, luts);
     __syncthreads();
   }
   const WaveTask t = wave_task(a);
-  if (!t.valid) return;
-  const int lane = t.lane;
-  const int ys = t.ys, ye = t.ye;
-  const int cb = tile_base<C>(a, t.xt, kOutChunks * 16) - 16 + lane * 16;
-  const uint32_t lane_in = cb < a.E + 16 ? (uint32_t)(cb * CIN) : kOOB;
-  const OutLanes lout = out_lanes<EXP>(a, lane, cb - 16 * lane);
-  const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.in_base, a.in_bytes);
-  const __amdgpu_buffer_rsrc_t rout = make_rsrc(a.out_base, a.out_bytes);
-  const uint32_t last_row = in_row_off(a, ye - 1 + R);
-  __shared__ __attribute__((aligned(16))) uint4 xbuf[EXP ? kWaves : 1][EXP ? 3 * kW : 1];
-  uint4* xb = xbuf[EXP ? t.wave : 0];
-
-  uint32_t keep[SKIP ? 4 : 1];
-  if constexpr (SKIP) skip_cols<C>(a, cb, R, keep);
-  uint32_t ring[K][NE];  // slot of input row r: (r - (ys - R)) mod K
-  auto push = [&](const RawChunk<PRO>& raw, uint32_t (&slot)[NE]) __attribute__((always_inline)) {
-    uint32_t u[8];
-    cook_pairs<PRO>(a, raw, luts, u);
-    extend_row<NX>(u, slot);
-  };
-#pragma unroll
-  for (int i = 0; i < K - 1; ++i) {  // rows ys-R .. ys+R-1
-    RawChunk<PRO> r;
-    load_raw<PRO>(rin, in_row_off(a, ys - R + i), lane_in, r);
-    push(r, ring[i]);
-  }
-  RawChunk<PRO> nx[K];  // row y + o + R for the step o of the current round
-#pragma unroll
-  for (int o = 0; o < K; ++o) load_raw<PRO>(rin, ys + o < ye ? in_row_off(a, ys + o + R) : last_row, lane_in, nx[o]);
-
-  const bool inner = rows_inside(a, ys - R, ye - 1 + R);
-  for (int y = ys; y < ye; y += K) {
-#pragma unroll
-    for (int o = 0; o < K; ++o) {
-      const int yy = y + o;
-      push(nx[o], ring[(o + K - 1) % K]);
-      load_raw<PRO>(rin, ahead_row_off(a, inner, yy, K, ye, R, last_row), lane_in, nx[o]);
-      uint32_t h[8];
-      rank_row<C, F, NX, NE>(ring, h);
-      uint32_t o4[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) o4[q] = __builtin_amdgcn_perm(h[2 * q + 1], h[2 * q], 0x06040200u);
-      if constexpr (SKIP) {
-        uint32_t center[4];
-        const uint32_t(&cr)[NE] = ring[(o + R) % K];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) center[q] = __builtin_amdgcn_perm(cr[NX + 2 * q + 1], cr[NX + 2 * q], 0x06040200u);
-        apply_skip(a, a.row0 + yy, R, keep, center, o4);
-      }
-      if (a.has_epi) lut16(luts + 512, o4);
-      store_out<EXP, SAUX>(o4, rout, yy < ye, a.out_org + (uint32_t)((int64_t)yy * a.out_pitch), lout, xb, lane);
-    }
-  }
-  band_margins<C, EXP ? 3 : C>(a, t);
+  if (t.valid) ring_task<C, F, PRO, SKIP, SAUX, EXP>(a, t, luts, xbuf[EXP ? t.wave : 0], RankRow<C, F>{});
 }
 
 // Launch geometry and occupancy cap as for the direct family (plan_bands,
 // kNtWgsDirect on HBM-streaming launches without a gray prologue).
 template <int C, class F, int PRO, bool EXP>
 void launch_rank(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s) {
-  using K = void (*)(KArgs);
-  const K fns[4] = {k_rank<C, F, PRO, false, 0, EXP>, k_rank<C, F, PRO, false, kNtAux, EXP>,
-                    k_rank<C, F, PRO, true, 0, EXP>, k_rank<C, F, PRO, true, kNtAux, EXP>};
-  const K fn = fns[2 * skip + nt];
-  dim3 grid;
-  plan_bands(a, grid, tiles, n0, n1, band, F::R, resident_slots((const void*)fn));
-  fn<<<grid, kNT, nt_lds_reserve((const void*)fn, stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect)), s>>>(a);
+  const KernelFn fns[4] = {k_rank<C, F, PRO, false, 0, EXP>, k_rank<C, F, PRO, false, kNtAux, EXP>,
+                           k_rank<C, F, PRO, true, 0, EXP>, k_rank<C, F, PRO, true, kNtAux, EXP>};
+  launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R,
+               stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect), s);
 }
 
 }  // namespace dev

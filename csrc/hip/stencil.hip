@@ -114,11 +114,23 @@ __global__ __launch_bounds__(kNT, 2) void k_conv_small(ConvSmallArgs ca) {
 
 }  // namespace dev
 
-void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
-  dev::KArgs a{};
+namespace {
+// The part of the argument block every wave-tile launch fills the same way:
+// geometry, border, the buffer-descriptor view (checked) and the output row
+// ranges.  n0 / n1: rows of the two ranges; tiles: wave tiles per row.
+struct TileLaunch {
+  int n0, n1, tiles;
+};
+TileLaunch fill_tile_args(const Pass& p, const PassLaunch& L, dev::KArgs& a) {
+  STRIPE_CHECK(p.cmid == 1 || p.cmid == 3, "wave-tile launch: channels must be 1 or 3");
+  STRIPE_CHECK(L.in_base && L.out_base, "wave-tile launch needs the allocation view (in_base/out_base)");
+  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_bytes > 0 &&
+                   L.out_bytes < (int64_t)dev::kOOB,
+               "stripe buffers must be < 2 GiB for buffer-descriptor addressing");
+  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
+               "bad origin offsets");
   a.in = L.in;
   a.out = L.out;
-  a.luts = pc.luts;
   a.zero_row = L.zero_row;
   a.in_pitch = L.in_pitch;
   a.out_pitch = L.out_pitch;
@@ -128,6 +140,27 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
   a.row0 = L.row0;
   a.Hg = L.Hg;
   a.border = (int)p.border;
+  a.in_base = L.in_base;
+  a.out_base = L.out_base;
+  a.in_bytes = (uint32_t)L.in_bytes;
+  a.in_org = (uint32_t)L.in_org;
+  a.in_zero = (uint32_t)L.in_zero;
+  a.out_bytes = (uint32_t)L.out_bytes;
+  a.out_org = (uint32_t)L.out_org;
+  const int n0 = std::max(0, L.ry[1] - L.ry[0]);
+  const int n1 = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
+  a.ry0 = L.ry[0];
+  a.ry1 = L.ry[0] + n0;
+  a.ry2 = n1 ? L.ry[2] : 0;
+  a.ry3 = n1 ? L.ry[3] : 0;
+  return {n0, n1, (int)div_up(a.E, dev::kOutChunks * 16)};
+}
+}  // namespace
+
+void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
+  dev::KArgs a{};
+  const auto [n0, n1, tiles] = fill_tile_args(p, L, a);
+  a.luts = pc.luts;
   a.out_px = p.out_margin_px;
   a.out_border = (int)p.out_margin_border;
   a.has_pre = 0;
@@ -144,30 +177,8 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
     a.gshift[c] = gp.shift[c];
     STRIPE_CHECK(gp.mult[c] < (1u << 24), "gray multiplier exceeds 24 bits");
   }
-  STRIPE_CHECK(p.cmid == 1 || p.cmid == 3, "stencil channels must be 1 or 3");
   STRIPE_CHECK(!(p.pro.gray && p.cin != 3), "gray prologue needs 3 input channels");
-  STRIPE_CHECK(L.in_base && L.out_base, "stencil launch needs the allocation view (in_base/out_base)");
-  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_bytes > 0 &&
-                   L.out_bytes < (int64_t)dev::kOOB,
-               "stripe buffers must be < 2 GiB for buffer-descriptor addressing");
-  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
-               "bad origin offsets");
-  a.in_base = L.in_base;
-  a.out_base = L.out_base;
-  a.in_bytes = (uint32_t)L.in_bytes;
-  a.in_org = (uint32_t)L.in_org;
-  a.in_zero = (uint32_t)L.in_zero;
-  a.out_bytes = (uint32_t)L.out_bytes;
-  a.out_org = (uint32_t)L.out_org;
-
-  const int n0 = std::max(0, L.ry[1] - L.ry[0]);
-  const int n1 = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
   if (n0 + n1 == 0) return;
-  const int tiles = (int)div_up(a.E, dev::kOutChunks * 16);  // wave tiles per row
-  a.ry0 = L.ry[0];
-  a.ry1 = L.ry[0] + n0;
-  a.ry2 = n1 ? L.ry[2] : 0;
-  a.ry3 = n1 ? L.ry[3] : 0;
   const int band = L.band;
   // Output stores bypass the caches (nt) when the pass streams more than the
   // Infinity Cache holds: then the next pass cannot hit in it anyway (16K RGB
@@ -246,41 +257,11 @@ bool conv_small_supported(const Pass& p) {
 
 void launch_conv_small(const Pass& p, const PassLaunch& L, hipStream_t s) {
   STRIPE_CHECK(conv_small_supported(p), "conv pass not eligible for the direct VALU kernel");
-  STRIPE_CHECK(L.in_base && L.out_base, "conv launch needs the allocation view (in_base/out_base)");
-  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_bytes > 0 &&
-                   L.out_bytes < (int64_t)dev::kOOB,
-               "stripe buffers must be < 2 GiB for buffer-descriptor addressing");
-  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
-               "bad origin offsets");
   dev::ConvSmallArgs ca{};
   dev::KArgs& a = ca.a;
-  a.in = L.in;
-  a.out = L.out;
-  a.zero_row = L.zero_row;
-  a.in_pitch = L.in_pitch;
-  a.out_pitch = L.out_pitch;
-  a.W = L.W;
-  a.E = L.W * p.cmid;
-  a.rows = L.rows;
-  a.row0 = L.row0;
-  a.Hg = L.Hg;
-  a.border = (int)p.border;
-  a.in_base = L.in_base;
-  a.out_base = L.out_base;
-  a.in_bytes = (uint32_t)L.in_bytes;
-  a.in_org = (uint32_t)L.in_org;
-  a.in_zero = (uint32_t)L.in_zero;
-  a.out_bytes = (uint32_t)L.out_bytes;
-  a.out_org = (uint32_t)L.out_org;
+  const auto [n0, n1, tiles] = fill_tile_args(p, L, a);
   for (int i = 0; i < p.K * p.K; ++i) ca.w[i] = p.conv_w[(size_t)i];
-  const int n0 = std::max(0, L.ry[1] - L.ry[0]);
-  const int n1 = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
   if (n0 + n1 == 0) return;
-  const int tiles = (int)div_up(a.E, dev::kOutChunks * 16);
-  a.ry0 = L.ry[0];
-  a.ry1 = L.ry[0] + n0;
-  a.ry2 = n1 ? L.ry[2] : 0;
-  a.ry3 = n1 ? L.ry[3] : 0;
   const int64_t pass_bytes = (int64_t)(n0 + n1) * L.W * 2 * p.cmid;
   bool nt = pass_bytes > dev::kNtMinBytes;
   if (const char* e = std::getenv("STRIPE_NT")) nt = std::atoi(e) != 0;
@@ -295,7 +276,7 @@ void launch_conv_small(const Pass& p, const PassLaunch& L, hipStream_t s) {
   STRIPE_CONV_SMALL(3, 5)
 #undef STRIPE_CONV_SMALL
   dim3 grid;
-  dev::plan_bands(a, grid, tiles, n0, n1, L.band > 0 ? L.band : 16, p.R, 0);
+  dev::plan_bands(a, grid, tiles, n0, n1, L.band > 0 ? L.band : 16, p.R);
   fn<<<grid, dev::kNT, 0, s>>>(ca);
   HIP_CHECK(hipGetLastError());
 }

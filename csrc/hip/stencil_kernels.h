@@ -1,6 +1,9 @@
-// Stencil kernels (k_sep, k_direct) and their launch templates, shared by
-// the instantiation units stencil_inst_*.hip (one group of filters each, so
-// the ~440 kernel instances compile in parallel) and stencil.hip.
+// Stencil kernels and their launch templates, shared by the instantiation
+// units stencil_inst_*.hip (one group of filters each, so the kernel instances
+// compile in parallel) and stencil.hip: k_sep (separable filters, sep_task),
+// k_sobel_rp (gray sobel on row pairs), k_direct (K x K taps) and ring_task,
+// the register-ring row walk of k_direct as a device function that takes the
+// row operation; k_rank (rank_kernels.h) is a wrapper of it.
 #pragma once
 
 // Integer stencil passes with fused pointwise prologue/epilogue (gfx950).
@@ -227,16 +230,6 @@ __device__ __forceinline__ void cook(const KArgs& a, const RawChunk<PRO>& r, con
   }
 }
 
-// Load + prologue in one step (rows that are consumed right away).
-template <int PRO>
-__device__ __forceinline__ void load_chunk(const KArgs& a, __amdgpu_buffer_rsrc_t rin, uint32_t row_off,
-                                           uint32_t lane_off, const uint8_t* lut_post, uint32_t (&o)[4]) {
-  RawChunk<PRO> r;
-  load_raw<PRO>(rin, row_off, lane_off, r);
-  cook<PRO>(a, r, lut_post, o);
-}
-
-template <int PRO>
 __device__ __forceinline__ void load_luts(const KArgs& a, uint8_t* lds) {
   for (int i = threadIdx.x; i < 768; i += (int)blockDim.x) lds[i] = a.luts[i];
 }
@@ -772,7 +765,7 @@ __global__ __launch_bounds__(kNT, (F::K >= 7 ? 2 : (SKIP && EXP ? 3 : 4))) void 
   __shared__ __attribute__((aligned(16))) uint4 xbuf[EXP ? kWaves : 1][EXP ? 3 * kW : 1];
   __shared__ uint8_t luts[768];
   if (PRO != PRO_NONE || a.has_epi) {
-    load_luts<PRO>(a, luts);
+    load_luts(a, luts);
     __syncthreads();
   }
   const WaveTask t = MODE == kRuns ? runs_task(a) : wave_task(a);
@@ -966,13 +959,17 @@ __global__ __launch_bounds__(kNT, 4) void k_sobel_rp(KArgs a) {
 }
 
 // ------------------------------------------------------------------------------
-// Direct (non-separable) filters: emboss3/5, sharpen, laplace
+// K x K window filters: the register-ring row walk of the direct filters
+// (emboss3/5, sharpen, laplace: k_direct) and the rank filters (ring_task, k_rank)
 // ------------------------------------------------------------------------------
-// The last K input rows live in registers, unpacked to u16 pairs and extended
-// by the neighbour lanes' edge dwords (DPP wave shifts: no LDS, no wave sync);
-// every tap is one packed i16 multiply-add per two outputs (|sum| <= 17*255).
-// The y loop is unrolled K times so the register ring is indexed statically,
-// and the K raw rows of the next round are in flight meanwhile.
+// The last K input rows live in registers, prologue applied, unpacked to u16
+// pairs and extended by the neighbour lanes' edge dwords (DPP wave shifts: no
+// LDS, no wave sync).  The y loop is unrolled K times so the register ring is
+// indexed statically, and the K raw rows of the next round are in flight
+// meanwhile (loads past the band re-read its last input row).  A row operation
+// turns the ring into the lane's output pairs; the walk packs them to bytes,
+// merges the @skip centre, applies the epilogue LUT and stores the row, and
+// after the band the edge waves rewrite the output margins.
 template <int NX>
 __device__ __forceinline__ void extend_row(const uint32_t (&u)[8], uint32_t (&e)[8 + 2 * NX]) {
 #pragma unroll
@@ -986,6 +983,85 @@ __device__ __forceinline__ void extend_row(const uint32_t (&u)[8], uint32_t (&e)
   for (int i = 0; i < 8; ++i) e[NX + i] = u[i];
 }
 
+// Geometry of the extended ring rows of a C-channel K x K window.
+template <int C, class F>
+struct RingDims {
+  static constexpr int NX = (F::R * C + 1) / 2;  // neighbour dwords per side
+  static constexpr int NE = 8 + 2 * NX;          // extended row dwords
+};
+
+// One wave task (a band of rows of one tile column) of a K x K window filter:
+// the walk of k_rank (rank_kernels.h) and, as text, of k_direct below.  `row_op(ring, o, h)`
+// turns the ring into the lane's 8 output pairs of one row; o is the unrolled
+// step (a compile-time constant after unrolling): ring[(o + dy) % K] holds
+// window row dy.
+template <int C, class F, int PRO, bool SKIP, int SAUX, bool EXP, class RowOp>
+__device__ __forceinline__ void ring_task(const KArgs& a, const WaveTask& t, const uint8_t* luts, uint4* xb,
+                                          RowOp row_op) {
+  static_assert(!EXP || C == 1, "expand epilogue needs a 1-channel stencil");
+  constexpr int R = F::R, K = F::K;
+  constexpr int NX = RingDims<C, F>::NX, NE = RingDims<C, F>::NE;
+  constexpr int CIN = is_gray(PRO) ? 3 : 1;
+  const int lane = t.lane;
+  const int ys = t.ys, ye = t.ye;
+  const int cb = tile_base<C>(a, t.xt, kOutChunks * 16) - 16 + lane * 16;
+  const uint32_t lane_in = cb < a.E + 16 ? (uint32_t)(cb * CIN) : kOOB;
+  const OutLanes lout = out_lanes<EXP>(a, lane, cb - 16 * lane);
+  const __amdgpu_buffer_rsrc_t rin = make_rsrc(a.in_base, a.in_bytes);
+  const __amdgpu_buffer_rsrc_t rout = make_rsrc(a.out_base, a.out_bytes);
+  const uint32_t last_row = in_row_off(a, ye - 1 + R);
+
+  uint32_t keep[SKIP ? 4 : 1];
+  if constexpr (SKIP) skip_cols<C>(a, cb, R, keep);
+  uint32_t ring[K][NE];  // slot of input row r: (r - (ys - R)) mod K
+  auto push = [&](const RawChunk<PRO>& raw, uint32_t (&slot)[NE]) __attribute__((always_inline)) {
+    uint32_t u[8];
+    cook_pairs<PRO>(a, raw, luts, u);
+    extend_row<NX>(u, slot);
+  };
+#pragma unroll
+  for (int i = 0; i < K - 1; ++i) {  // rows ys-R .. ys+R-1
+    RawChunk<PRO> r;
+    load_raw<PRO>(rin, in_row_off(a, ys - R + i), lane_in, r);
+    push(r, ring[i]);
+  }
+  RawChunk<PRO> nx[K];  // row y + o + R for the step o of the current round
+#pragma unroll
+  for (int o = 0; o < K; ++o) load_raw<PRO>(rin, ys + o < ye ? in_row_off(a, ys + o + R) : last_row, lane_in, nx[o]);
+
+  const bool inner = rows_inside(a, ys - R, ye - 1 + R);
+  for (int y = ys; y < ye; y += K) {
+#pragma unroll
+    for (int o = 0; o < K; ++o) {
+      const int yy = y + o;
+      push(nx[o], ring[(o + K - 1) % K]);
+      load_raw<PRO>(rin, ahead_row_off(a, inner, yy, K, ye, R, last_row), lane_in, nx[o]);
+      uint32_t h[8];
+      row_op(ring, o, h);
+      uint32_t o4[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o4[q] = __builtin_amdgcn_perm(h[2 * q + 1], h[2 * q], 0x06040200u);
+      if constexpr (SKIP) {
+        uint32_t center[4];
+        const uint32_t(&cr)[NE] = ring[(o + R) % K];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) center[q] = __builtin_amdgcn_perm(cr[NX + 2 * q + 1], cr[NX + 2 * q], 0x06040200u);
+        apply_skip(a, a.row0 + yy, R, keep, center, o4);
+      }
+      if (a.has_epi) lut16(luts + 512, o4);
+      store_out<EXP, SAUX>(o4, rout, yy < ye, a.out_org + (uint32_t)((int64_t)yy * a.out_pitch), lout, xb, lane);
+    }
+  }
+  band_margins<C, EXP ? 3 : C>(a, t);
+}
+
+// The direct filters keep a body of their own, the same walk with the taps in
+// place: every tap is one packed i16 multiply-add per two outputs (|sum| <=
+// 17*255), taps are compile-time literals (zero taps vanish).  As a wrapper of
+// ring_task, 68 of the 160 instances changed their register count and one
+// (1-channel emboss3, LUT prologue, expand epilogue: 80 -> 81 VGPRs, 6 -> 5
+// waves per SIMD) ran 1.1 % slower (profiles/ringwalk/README.md).  A change to
+// the walk is made here and in ring_task.
 template <int C, class F, int PRO, bool SKIP, int SAUX, bool EXP = false>
 __global__ __launch_bounds__(kNT, (F::K >= 5 ? 3 : 4)) void k_direct(KArgs a) {
   static_assert(!EXP || C == 1, "expand epilogue needs a 1-channel stencil");
@@ -995,7 +1071,7 @@ __global__ __launch_bounds__(kNT, (F::K >= 5 ? 3 : 4)) void k_direct(KArgs a) {
   constexpr int CIN = is_gray(PRO) ? 3 : 1;
   __shared__ uint8_t luts[768];
   if (PRO != PRO_NONE || a.has_epi) {
-    load_luts<PRO>(a, luts);
+    load_luts(a, luts);
     __syncthreads();
   }
   const WaveTask t = wave_task(a);
@@ -1044,8 +1120,6 @@ __global__ __launch_bounds__(kNT, (F::K >= 5 ? 3 : 4)) void k_direct(KArgs a) {
         for (int dy = 0; dy < K; ++dy)
 #pragma unroll
           for (int dx = 0; dx < K; ++dx) {
-            constexpr int unused = 0;
-            (void)unused;
             const int w = F::w(dy, dx);
             if (w == 0) continue;
             const i16x2 v = as_i16x2(pair_at(ring[(o + dy) % K], 2 * NX + 2 * pp + (dx - R) * C));
@@ -1076,23 +1150,6 @@ __global__ __launch_bounds__(kNT, (F::K >= 5 ? 3 : 4)) void k_direct(KArgs a) {
 // ------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------
-// Resident workgroups per device for a kernel (occupancy x CUs), cached.
-inline int resident_slots(const void* fn) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, int>, int> cache;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({fn, dev});
-  if (it != cache.end()) return it->second;
-  int per_cu = 0, cus = 0;
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kNT, 0));
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int slots = std::max(1, per_cu) * std::max(1, cus);
-  cache[{fn, dev}] = slots;
-  return slots;
-}
-
 // Launch geometry: band height a multiple of 4 (rows are stepped in groups of 4).
 // Default band height: short bands keep the rows all resident workgroups touch
 // at once in a compact window (measured on MI355X, 16384-wide RGB: gaussian5
@@ -1111,8 +1168,7 @@ inline int env_nxcd() {
   return v;
 }
 
-inline void plan_bands(KArgs& a, dim3& grid, int tiles, int n0, int n1, int band, int R, int slots) {
-  (void)slots;
+inline void plan_bands(KArgs& a, dim3& grid, int tiles, int n0, int n1, int band, int R) {
   if (env_nxcd() >= 0) a.nxcd = env_nxcd();
   if (band <= 0) band = R >= 3 ? 16 : 12;
   band = (int)align_up(band, 4);
@@ -1169,6 +1225,18 @@ inline int stencil_cap(bool nt, int wgs, int family_default) {
   return nt ? family_default : 0;
 }
 
+// Plans the bands of one launch (plan_bands) and starts fn over them with at
+// most `cap` workgroups per CU (nt_lds_reserve; 0 = no cap).  grid_of: the
+// grid for the planned bands where it is not plan_bands' own (kRuns).
+using KernelFn = void (*)(KArgs);
+inline void launch_bands(KernelFn fn, KArgs a, int tiles, int n0, int n1, int band, int R, int cap, hipStream_t s,
+                         int64_t (*grid_of)(int ntx, int nbands) = nullptr) {
+  dim3 grid;
+  plan_bands(a, grid, tiles, n0, n1, band, R);
+  if (grid_of) grid = dim3((unsigned)grid_of(tiles, a.nbands));
+  fn<<<grid, kNT, nt_lds_reserve((const void*)fn, cap), s>>>(a);
+}
+
 // Rank filters (sdef::RankDef: median / erode / dilate) have their own kernel
 // family, k_rank; launch_rank is defined in rank_kernels.h, which the unit
 // that instantiates those filters includes (stencil_inst_e.hip).
@@ -1186,17 +1254,14 @@ void launch_rank(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1
 template <int C, class F, int PRO, bool EXP = false>
 void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s,
                 int order = 0) {
-  using K = void (*)(KArgs);
-  dim3 grid;
+  using K = KernelFn;
   if constexpr (F::SEP && PRO == PRO_NONE && !EXP) {
     if constexpr (SepTraits<F>::SYM) {
       if (order == 1) {  // kRuns (runs_task); the remap is its own
         const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP, kRuns>, k_sep<C, F, PRO, false, kNtAux, EXP, kRuns>,
                           k_sep<C, F, PRO, true, 0, EXP, kRuns>, k_sep<C, F, PRO, true, kNtAux, EXP, kRuns>};
-        const K fn = fns[2 * skip + nt];
-        plan_bands(a, grid, tiles, n0, n1, band, F::R, 0);
-        grid = dim3((unsigned)runs_grid(tiles, a.nbands));
-        fn<<<grid, kNT, nt_lds_reserve((const void*)fn, stencil_cap(nt, wgs, kNtWgsSep)), s>>>(a);
+        launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s,
+                     runs_grid);
         return;
       }
     }
@@ -1234,8 +1299,7 @@ void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1,
         const K fn = fns[wide][pb == 8 ? 1 : pb == 12 ? 2 : 0][nt];
         if (pb) band = pb;
         if (wide) tiles = (int)div_up((int64_t)a.E, kW * 16);
-        plan_bands(a, grid, tiles, n0, n1, band, F::R, 0);
-        fn<<<grid, kNT, nt_lds_reserve((const void*)fn, stencil_cap(nt, wgs, kNtWgsSep)), s>>>(a);
+        launch_bands(fn, a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s);
         return;
       }
     }
@@ -1245,15 +1309,12 @@ void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1,
   } else if constexpr (F::SEP) {
     const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP>, k_sep<C, F, PRO, false, kNtAux, EXP>,
                       k_sep<C, F, PRO, true, 0, EXP>, k_sep<C, F, PRO, true, kNtAux, EXP>};
-    const K fn = fns[2 * skip + nt];
-    plan_bands(a, grid, tiles, n0, n1, band, F::R, resident_slots((const void*)fn));
-    fn<<<grid, kNT, nt_lds_reserve((const void*)fn, stencil_cap(nt, wgs, kNtWgsSep)), s>>>(a);
+    launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s);
   } else {
     const K fns[4] = {k_direct<C, F, PRO, false, 0, EXP>, k_direct<C, F, PRO, false, kNtAux, EXP>,
                       k_direct<C, F, PRO, true, 0, EXP>, k_direct<C, F, PRO, true, kNtAux, EXP>};
-    const K fn = fns[2 * skip + nt];
-    plan_bands(a, grid, tiles, n0, n1, band, F::R, resident_slots((const void*)fn));
-    fn<<<grid, kNT, nt_lds_reserve((const void*)fn, stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect)), s>>>(a);
+    launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R,
+                 stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect), s);
   }
 }
 

@@ -336,7 +336,7 @@ static void launch_sep(const SepCfg& c, const Frame& f, hipStream_t s, uint32_t*
   const int tiles = (int)div_up(a.E, kOutChunks * 16);
   dim3 grid;
   const SepFn fn = c.mode == 9 ? k_band_copy<2> : sep_fn(c.saux, c.mode, stamps != nullptr, c.nw);
-  plan_bands(a, grid, tiles, g_rows, 0, c.band, g_sobel ? 1 : 2, 0);
+  plan_bands(a, grid, tiles, g_rows, 0, c.band, g_sobel ? 1 : 2);
   grid.x = (unsigned)(c.mode == kQuad   ? (int64_t)tiles * div_up(a.nbands, 4)
                       : c.mode == kRuns ? runs_grid(tiles, a.nbands)
                                         : div_up((int64_t)tiles * a.nbands, c.nw));
@@ -414,7 +414,7 @@ static void launch_pat(const PatCfg& c, const Frame& f, hipStream_t s) {
   a.ry1 = g_rows;
   const int tiles = (int)div_up(a.E, kW * c.lb);
   dim3 grid;
-  plan_bands(a, grid, tiles, g_rows, 0, c.band, 2, 0);
+  plan_bands(a, grid, tiles, g_rows, 0, c.band, 2);
   a.nxcd = 0;
   void (*fn)(KArgs) = pat_fn(c);
   fn<<<grid, kNT, nt_lds_reserve((const void*)fn, c.cap), s>>>(a);

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(NW * kW, (F::K >= 7 ? 2 : (SKIP && EXP ? 3 : 4))) v
   __shared__ __attribute__((aligned(16))) uint4 xbuf[EXP ? NW : 1][EXP ? 3 * kW : 1];
   __shared__ uint8_t luts[768];
   if (PRO != PRO_NONE || a.has_epi) {
-    load_luts<PRO>(a, luts);
+    load_luts(a, luts);
     __syncthreads();
   }
   if constexpr (MODE == kQueue) {
