@@ -44,7 +44,7 @@ std::array<uint8_t, 256> identity_lut() {
 
 // Fold a per-channel LUT op into `prog` at its current position.
 void fold_lut(PointwiseProgram& prog, const Op& op) {
-  if (!prog.gray) {
+  if (!prog.gray && !prog.cmat) {
     if (!prog.has_pre) {
       prog.pre = identity_lut();
       prog.has_pre = true;
@@ -59,9 +59,15 @@ void fold_lut(PointwiseProgram& prog, const Op& op) {
   }
 }
 
-// Without a gray stage pre and post are one per-channel LUT: keep it in `post`.
+// Without a gray or matrix stage pre and post are one per-channel LUT: keep it
+// in `post`.  A matrix that is exactly the identity (q = 4096 I, no offsets) is dropped.
 void normalize(PointwiseProgram& prog) {
-  if (!prog.gray && prog.has_pre) {
+  if (prog.cmat) {
+    bool id = true;
+    for (int i = 0; i < 12; ++i) id = id && prog.cm[(size_t)i] == (i < 9 && i % 4 == 0 ? 4096 : 0);
+    if (id) prog.cmat = false;
+  }
+  if (!prog.gray && !prog.cmat && prog.has_pre) {
     std::array<uint8_t, 256> l{};
     for (int i = 0; i < 256; ++i) l[i] = prog.has_post ? prog.post[prog.pre[i]] : prog.pre[i];
     prog.post = l;
@@ -81,6 +87,7 @@ std::string prog_desc(const PointwiseProgram& p) {
   std::string s;
   if (p.has_pre) s += "lut,";
   if (p.gray) s += p.gmode == GrayMode::Ref ? "gray:ref," : "gray:bt601,";
+  if (p.cmat) s += "cmat,";
   if (p.has_post) s += "lut,";
   if (p.expand) s += "expand,";
   if (!s.empty()) s.pop_back();
@@ -128,7 +135,8 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
       switch (op.kind) {
         case OpKind::Gray:
           if (c == 1) break;  // gray of gray is the identity
-          if (pending.expand || (!fuse && !pending.identity())) flush_pointwise();
+          // (a pending matrix is rounded and saturated: gray of it is a second stage)
+          if (pending.expand || pending.cmat || (!fuse && !pending.identity())) flush_pointwise();
           pending.gray = true;
           pending.gmode = op.gray;
           c = 1;
@@ -138,6 +146,14 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
           if (!fuse && !pending.identity()) flush_pointwise();
           pending.expand = true;
           c = 3;
+          break;
+        case OpKind::ColorMatrix:
+          STRIPE_CHECK(c == 3, "'" << op.text << "' needs a 3-channel image (on a gray image: after expand)");
+          // one matrix per program, in gray's slot: two rounded, saturated maps
+          // do not compose exactly, and expand is the program's last stage
+          if (pending.cmat || pending.gray || pending.expand || (!fuse && !pending.identity())) flush_pointwise();
+          pending.cmat = true;
+          std::copy(op.cm, op.cm + 12, pending.cm.begin());
           break;
         default:
           // a LUT after expand equals the same LUT before it (channels are copies)
@@ -200,7 +216,7 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     Pass* last = plan.passes.empty() ? nullptr : &plan.passes.back();
     const bool epi_ok = fuse && last &&
                         (last->kind == PassKind::Separable || last->kind == PassKind::Direct) &&
-                        !last->has_epi && !last->epi_expand && !pending.gray && !pending.has_pre &&
+                        !last->has_epi && !last->epi_expand && !pending.gray && !pending.cmat && !pending.has_pre &&
                         (!pending.expand || last->cmid == 1);
     if (epi_ok) {
       if (pending.has_post) {

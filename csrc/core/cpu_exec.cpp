@@ -32,10 +32,29 @@ inline int isqrt_round(int n) {
   return n > k * k + k ? k + 1 : k;
 }
 
-// The pointwise program as byte tables: per pixel out = post(gray(pre(px))).
+// Hot loops, each cloned for AVX2 and a baseline x86-64 target (the loader
+// picks the AVX2 clone where the CPU has it; this file is host-only C++).
+#define STRIPE_SIMD __attribute__((target_clones("avx2", "default")))
+
+// Colour matrix sweep over n RGB pixels: golden apply_prog's formula
+// (color_matrix_channel) in i32, q = 9 coefficients then 3 offsets.
+STRIPE_SIMD void cmat_sweep(const uint8_t* __restrict s, uint8_t* __restrict o, const int32_t* __restrict q, int n) {
+  const int32_t h = 1 << (kColorShift - 1);
+  for (int x = 0; x < n; ++x) {
+    const int32_t r = s[3 * x], g = s[3 * x + 1], b = s[3 * x + 2];
+    for (int c = 0; c < 3; ++c) {
+      const int32_t v = (q[3 * c] * r + q[3 * c + 1] * g + q[3 * c + 2] * b + q[9 + c] + h) >> kColorShift;
+      o[3 * x + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    }
+  }
+}
+
+// The pointwise program as byte tables: per pixel out = post((gray | cmat)(pre(px))).
 struct ProgTables {
   int cin = 3, cmid = 3;
   bool gray = false, ref = false, copy = false;
+  bool cmat = false, cm_pre = false, cm_post = false;
+  int32_t cm[12];
   uint8_t pre[256], lut[256];         // lut: post(pre(v)) (no gray) or post(v) (gray)
   uint8_t tr[256], tg[256], tb[256];  // gray:ref: the per-channel truncated terms of pre(v)
 
@@ -43,10 +62,16 @@ struct ProgTables {
     gray = pr.gray;
     cmid = gray ? 1 : cin;
     ref = pr.gmode == GrayMode::Ref;
-    copy = !gray;
+    cmat = pr.cmat;
+    cm_pre = cmat && pr.has_pre;
+    cm_post = cmat && pr.has_post;
+    for (int i = 0; i < 12; ++i) cm[i] = pr.cm[(size_t)i];
+    copy = !gray && !cmat;
     for (int v = 0; v < 256; ++v) {
       pre[v] = pr.has_pre ? pr.pre[v] : (uint8_t)v;
-      if (!gray) {
+      if (cmat) {
+        lut[v] = pr.has_post ? pr.post[v] : (uint8_t)v;
+      } else if (!gray) {
         lut[v] = pr.has_post ? pr.post[pre[v]] : pre[v];
         copy = copy && lut[v] == v;
       } else {
@@ -61,7 +86,21 @@ struct ProgTables {
 
   // n pixels of cin bytes -> n pixels of cmid bytes
   void row(const uint8_t* src, int n, uint8_t* dst) const {
-    if (!gray) {
+    if (cmat) {
+      uint8_t t[3 * 256];  // pre-LUT pixels of one block
+      for (int x0 = 0; x0 < n; x0 += 256) {
+        const int m = std::min(256, n - x0);
+        const uint8_t* s = src + (size_t)3 * x0;
+        uint8_t* d = dst + (size_t)3 * x0;
+        if (cm_pre) {
+          for (int i = 0; i < 3 * m; ++i) t[i] = pre[s[i]];
+          s = t;
+        }
+        cmat_sweep(s, d, cm, m);
+        if (cm_post)
+          for (int i = 0; i < 3 * m; ++i) d[i] = lut[d[i]];
+      }
+    } else if (!gray) {
       const int nb = n * cin;
       if (copy) {
         std::memcpy(dst, src, (size_t)nb);
@@ -143,10 +182,6 @@ void ext_row(const Pass& p, const ProgTables& pt, ConstView in, int W, RowGeom g
     }
   }
 }
-
-// Hot loops, each cloned for AVX2 and a baseline x86-64 target (the loader
-// picks the AVX2 clone where the CPU has it; this file is host-only C++).
-#define STRIPE_SIMD __attribute__((target_clones("avx2", "default")))
 
 STRIPE_SIMD void tap_u8(int32_t* __restrict a, const uint8_t* __restrict s, int w, int n) {
   for (int i = 0; i < n; ++i) a[i] += w * (int32_t)s[i];

@@ -120,6 +120,20 @@ double parse_num(const std::string& s, const std::string& ctx) {
   return v;
 }
 
+// Quantise a colour matrix (row-major m, offsets b) into op.cm (filters.h).
+void set_color_matrix(Op& op, const double (&m)[9], const double (&b)[3], const std::string& tok) {
+  op.kind = OpKind::ColorMatrix;
+  for (int i = 0; i < 9; ++i) {
+    const double q = std::nearbyint(m[i] * 4096.0);
+    STRIPE_CHECK(std::fabs(q) <= 32767, "'" << tok << "': coefficient " << m[i] << " out of range (|m| < 8)");
+    op.cm[i] = (int)q;
+  }
+  for (int c = 0; c < 3; ++c) {
+    STRIPE_CHECK(std::fabs(b[c]) <= 2048, "'" << tok << "': offset " << b[c] << " out of range (|b| <= 2048)");
+    op.cm[9 + c] = (int)std::nearbyint(b[c] * 4096.0);
+  }
+}
+
 }  // namespace
 
 const StencilInfo& stencil_info(StencilId id) {
@@ -338,6 +352,68 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
       for (int i = 0; i < op.K; ++i)
         for (int j = 0; j < op.K; ++j) op.weights[(size_t)i * op.K + j] = op.sep_v[(size_t)i] * op.sep_h[(size_t)j];
       op.text = tok;
+    } else if (name == "colormatrix") {
+      // colormatrix:m00;m01;m02;m10;...;m22[:b0;b1;b2]  row-major, out_c = sum_k m[c][k] in_k + b_c
+      STRIPE_CHECK(parts.size() == 2 || parts.size() == 3,
+                   "'" << tok << "': colormatrix syntax: colormatrix:m00;m01;...;m22[:b0;b1;b2]");
+      double m[9], b[3] = {0, 0, 0};
+      const auto ms = split(parts[1], ';');
+      STRIPE_CHECK(ms.size() == 9, "'" << tok << "': colormatrix needs 9 coefficients, got " << ms.size());
+      for (int i = 0; i < 9; ++i) m[i] = parse_num(trim(ms[(size_t)i]), tok);
+      if (parts.size() == 3) {
+        const auto bs = split(parts[2], ';');
+        STRIPE_CHECK(bs.size() == 3, "'" << tok << "': colormatrix takes 3 offsets, got " << bs.size());
+        for (int i = 0; i < 3; ++i) b[i] = parse_num(trim(bs[(size_t)i]), tok);
+      }
+      set_color_matrix(op, m, b, tok);
+      op.text = tok;
+    } else if (name == "sepia") {
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': sepia takes no arguments");
+      const double m[9] = {.393, .769, .189, .349, .686, .168, .272, .534, .131}, b[3] = {0, 0, 0};
+      set_color_matrix(op, m, b, tok);
+      op.text = "sepia";
+    } else if (name == "swaprb" || name == "bgr") {
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
+      const double m[9] = {0, 0, 1, 0, 1, 0, 1, 0, 0}, b[3] = {0, 0, 0};
+      set_color_matrix(op, m, b, tok);
+      op.text = "swaprb";
+    } else if (name == "saturation" || name == "saturate") {
+      STRIPE_CHECK(parts.size() == 2, "'" << tok << "': saturation needs a factor, e.g. saturation:1.5");
+      const double S = parse_num(trim(parts[1]), tok);
+      // off-diagonals (1 - S) L_k; the diagonal takes what is left of 4096, so
+      // every row sums to exactly 1.0 and grey pixels are fixed points
+      const double L[3] = {.299, .587, .114};
+      op.kind = OpKind::ColorMatrix;
+      for (int c = 0; c < 3; ++c) {
+        int off = 0;
+        for (int k = 0; k < 3; ++k) {
+          if (k == c) continue;
+          const double q = std::nearbyint((1.0 - S) * L[k] * 4096.0);
+          STRIPE_CHECK(std::fabs(q) <= 32767, "'" << tok << "': saturation factor out of range");
+          op.cm[3 * c + k] = (int)q;
+          off += (int)q;
+        }
+        op.cm[3 * c + c] = 4096 - off;
+        STRIPE_CHECK(std::abs(op.cm[3 * c + c]) <= 32767, "'" << tok << "': saturation factor out of range");
+      }
+      op.fval = (float)S;
+      std::ostringstream os;
+      os << "saturation:" << op.fval;
+      op.text = os.str();
+    } else if (name == "ycbcr") {
+      // JFIF full-range RGB <-> YCbCr; the inverse folds the -128 terms into the offsets
+      const bool inv = parts.size() == 2 && trim(parts[1]) == "inv";
+      STRIPE_CHECK(parts.size() == 1 || inv, "'" << tok << "': ycbcr syntax: ycbcr or ycbcr:inv");
+      if (!inv) {
+        const double m[9] = {.299, .587, .114, -.168736, -.331264, .5, .5, -.418688, -.081312};
+        const double b[3] = {0, 128, 128};
+        set_color_matrix(op, m, b, tok);
+      } else {
+        const double m[9] = {1, 0, 1.402, 1, -.344136, -.714136, 1, 1.772, 0};
+        const double b[3] = {-1.402 * 128, .344136 * 128 + .714136 * 128, -1.772 * 128};
+        set_color_matrix(op, m, b, tok);
+      }
+      op.text = inv ? "ycbcr:inv" : "ycbcr";
     } else if (stencil_from_name(name, &sid)) {
       op.kind = OpKind::Stencil;
       op.sid = sid;
@@ -346,7 +422,8 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
       fail("unknown filter '" + name +
            "' (gray[:ref|bt601], contrast:F[:cv], invert, brightness:D, threshold:T, expand, "
            "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
-           "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb])");
+           "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
+           "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv])");
     }
     if (op.has_border) op.text += std::string("@") + border_name(op.border);
     ops.push_back(op);

@@ -25,6 +25,10 @@ inline void apply_prog(const PointwiseProgram& pr, const uint8_t* px, int cin, u
     STRIPE_CHECK(cin == 3, "gray needs 3 channels");
     v[0] = gray_pixel(pr.gmode, v[0], v[1], v[2]);
     n = 1;
+  } else if (pr.cmat) {
+    STRIPE_CHECK(cin == 3, "a colour matrix needs 3 channels");
+    const int r = v[0], g = v[1], b = v[2];
+    for (int c = 0; c < 3; ++c) v[c] = color_matrix_channel(pr.cm.data(), c, r, g, b);
   }
   if (pr.has_post)
     for (int c = 0; c < n; ++c) v[c] = pr.post[v[c]];

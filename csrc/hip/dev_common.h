@@ -48,6 +48,8 @@ struct KArgs {
   uint8_t* out_base;
   uint32_t in_bytes, in_org, in_zero;
   uint32_t out_bytes, out_org;
+  // colour matrix pass (k_colormix): q row-major, then qb (Q12, filters.h)
+  int cm[12];
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
@@ -130,6 +132,14 @@ __device__ __forceinline__ void band_range(const KArgs& a, int by, int& ys, int&
     ys = a.ry2 + (by - a.nb0) * a.band;
     ye = min(ys + a.band, a.ry3);
   }
+}
+
+// Orders this wave's LDS writes before its later LDS reads of other lanes' data
+// (LDS ops of one wave execute in order; this only stops compiler reordering).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {

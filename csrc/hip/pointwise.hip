@@ -1,4 +1,5 @@
-// Fused pointwise pass: out = expand?(post(gray?(pre(p)))) on 16 pixels per lane.
+// Fused pointwise pass: out = expand?(post(gray?(pre(p)))) on 16 pixels per lane;
+// a colour matrix in gray's slot runs on k_colormix below.
 //
 // Replaces the reference's separate grayscale and contrast launches
 // (kernel.cu:31-58, one thread per pixel, scalar u8 loads) with one pass of
@@ -155,6 +156,121 @@ __global__ __launch_bounds__(kNT) void k_pointwise_flat(KArgs a, int ngroups, in
     const u32x4v o = {t[0], t[1], t[2], t[3]};
     if constexpr (NT) __builtin_nontemporal_store(o, reinterpret_cast<u32x4v*>(drow + b0));
     else *reinterpret_cast<u32x4v*>(drow + b0) = o;
+  }
+}
+
+// Colour matrix pass, 3 -> 3 channels: out = post(cmat(pre(p))) with
+//   cmat_c = sat_u8((q[c][0] R + q[c][1] G + q[c][2] B + qb[c] + 2048) >> 12)
+// (filters.h color_matrix_channel).  Memory is moved as k_pointwise_flat moves
+// it: the row is a flat stream of 16-byte chunks, a wave owns 192 consecutive
+// chunks (3 KiB = 1024 pixels) and each of its 3 loads / 3 stores covers 1 KiB
+// contiguously, so nt stores write whole lines.  The arithmetic needs whole
+// pixels per lane, so the wave re-tiles its span through 3 KiB of LDS of its
+// own (the store_out<EXP> idiom of the stencil kernels: wave-synchronous, no
+// workgroup barrier): chunks 64 j + lane go in, lane l reads chunks 3 l + j =
+// pixels 16 l .. 16 l + 15, and the results travel back the same way.  The LUT
+// stages run on the flat chunks.  A pixel is two i16 pairs (R, G), (B, 0) and
+// an output channel two v_dot2 accumulations on qb + 2048, a shift and a clamp;
+// the 12 coefficients stay in scalar registers.
+// Chunk c covers row bytes [b_lo + 16 c, +16); b_lo = -48 with a left margin.
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int dot2_i16(uint32_t px, uint32_t k, int acc) {
+  return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, px), __builtin_bit_cast(s16x2, k), acc, false);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kNT) void k_colormix(KArgs a, int nchunks, int b_lo) {
+  __shared__ uint4 xb[3 * kNT];  // 3 KiB per wave
+  __shared__ uint8_t lut[512];
+  typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c0 = (blockIdx.x * (kNT / 64) + wave) * 192;  // first chunk of the wave's span
+  const int y = a.ry0 + blockIdx.y;
+  const uint8_t* srow = a.in + (int64_t)y * a.in_pitch + b_lo;
+  uint8_t* drow = a.out + (int64_t)y * a.out_pitch + b_lo;
+  u32x4v v[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int c = c0 + 64 * j + lane;
+    v[j] = u32x4v{0, 0, 0, 0};
+    if (c < nchunks) v[j] = *reinterpret_cast<const u32x4v*>(srow + 16 * c);
+  }
+  if (a.has_pre | a.has_post) {  // uniform: the loads above are in flight across the LUT fill
+    for (int i = threadIdx.x; i < 512; i += kNT) lut[i] = a.luts[i];
+    __syncthreads();
+  }
+  if (c0 >= nchunks) return;  // whole wave
+  uint4* w = xb + wave * 192;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t t[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+    if (a.has_pre) lut16(lut, t);
+    w[64 * j + lane] = make_uint4(t[0], t[1], t[2], t[3]);
+  }
+  wave_lds_sync();
+  uint32_t in[12];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const uint4 t = w[3 * lane + j];
+    in[4 * j] = t.x;
+    in[4 * j + 1] = t.y;
+    in[4 * j + 2] = t.z;
+    in[4 * j + 3] = t.w;
+  }
+  wave_lds_sync();  // reads done before the results overwrite the tile
+  uint32_t krg[3], kb[3];
+  int k0[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    krg[c] = ((uint32_t)a.cm[3 * c] & 0xFFFFu) | ((uint32_t)a.cm[3 * c + 1] << 16);
+    kb[c] = (uint32_t)a.cm[3 * c + 2] & 0xFFFFu;
+    k0[c] = a.cm[9 + c] + 2048;
+  }
+  int acc[48];  // Q12 sums in output byte order
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int b0 = 3 * i, d = b0 >> 2, o = b0 & 3;
+    const uint32_t lo = in[d], hi = in[d < 11 ? d + 1 : d];
+    // v_perm selectors: bytes 0..3 of lo, 4..7 of hi, 0x0c = zero
+    const uint32_t rg = __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | (uint32_t)o | ((uint32_t)(o + 1) << 16));
+    const uint32_t bz = __builtin_amdgcn_perm(hi, lo, 0x0c0c0c00u | (uint32_t)(o + 2));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[b0 + c] = dot2_i16(bz, kb[c], dot2_i16(rg, krg[c], k0[c]));
+  }
+  // floor shift and clamp to u8, two sums per instruction (gfx950 v_ashr_pk_u8_i32:
+  // sat_u8(s0 >> 12) | sat_u8(s1 >> 12) << 8)
+  uint32_t out[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const uint32_t h0 = __builtin_amdgcn_ashr_pk_u8_i32(acc[4 * i], acc[4 * i + 1], 12);
+    const uint32_t h1 = __builtin_amdgcn_ashr_pk_u8_i32(acc[4 * i + 2], acc[4 * i + 3], 12);
+    out[i] = h0 | (h1 << 16);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) w[3 * lane + j] = make_uint4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
+  wave_lds_sync();
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int c = c0 + 64 * j + lane;
+    const uint4 r = w[64 * j + lane];
+    uint32_t t[4] = {r.x, r.y, r.z, r.w};
+    if (a.has_post) lut16(lut + 256, t);
+    const int bb0 = b_lo + 16 * c;  // first row byte of the chunk (negative: left margin)
+    // constant-border margins hold zeros; reflect/replicate margins are processed
+    if (a.out_border == (int)Border::Constant && (bb0 < 0 || bb0 + 16 > a.W * 3)) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int bb = bb0 + i;
+        if (bb < 0 || bb >= a.W * 3) t[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
+      }
+    }
+    if (c < nchunks) {
+      const u32x4v ov = {t[0], t[1], t[2], t[3]};
+      if constexpr (NT) __builtin_nontemporal_store(ov, reinterpret_cast<u32x4v*>(drow + 16 * c));
+      else *reinterpret_cast<u32x4v*>(drow + 16 * c) = ov;
+    }
   }
 }
 
@@ -400,6 +516,7 @@ void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
     a.gmul[c] = gp.mult[c];
     a.gshift[c] = gp.shift[c];
   }
+  for (int i = 0; i < 12; ++i) a.cm[i] = p.pro.cm[(size_t)i];
   const int px = std::min(p.out_margin_px, kMaxRadius);
   const int g0 = px > 0 ? -1 : 0;  // one 16-pixel group of left margin
   const int ngroups = (int)div_up(L.W + px, 16) - g0;
@@ -437,7 +554,37 @@ void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
       if (nt) k_nt<<<grid, dev::kNT, resg, s>>>(a, ngroups, g0);
       else k_t<<<grid, dev::kNT, resg, s>>>(a, ngroups, g0);
     };
-    if (p.cin == p.cout && !gray) {
+    if (p.pro.cmat) {
+      // colour matrix: the byte range of the 16-pixel groups above (48 bytes
+      // each: 3 chunks) as a flat chunk stream, 192 chunks per wave
+      STRIPE_CHECK(p.cin == 3 && p.cout == 3 && !gray && !p.pro.expand, "colour matrix pass must be 3->3 channels");
+      const int nchunks = 3 * ngroups, b_lo = 48 * g0;
+      const bool big = (int64_t)(n0_rows + n1_rows) * L.W * 6 > dev::kNtMinBytes;
+      bool ntm = big;
+      if (const char* e = std::getenv("STRIPE_NT")) ntm = std::atoi(e) != 0;
+      // HBM-streaming launches: the residency cap of the flat passes below
+      // (STRIPE_PW_WGS; 0 = no cap).  Default 3 workgroups per CU for the bare
+      // matrix (16K RGB sepia 0.277 ms uncapped, 0.305 at 2, 0.269 at 3, 0.268
+      // at 4) and 6 with a LUT stage, whose LDS lookups need more waves in
+      // flight (invert,sepia,brightness:10: 0.411 at 2, 0.313 at 3, 0.292 at 4,
+      // 0.268 at 6, 0.271 uncapped; profiles/colormatrix/README.md)
+      static const int env_wgs = [] {
+        const char* e = std::getenv("STRIPE_PW_WGS");
+        return e ? std::atoi(e) : -1;
+      }();
+      const int mix_wgs = env_wgs >= 0 ? env_wgs : (p.pro.has_pre || p.pro.has_post ? 6 : 3);
+      size_t res = 0;
+      if (mix_wgs > 0 && big && ntm) {
+        int dev = 0, lds_cu = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+        const int64_t own = 3 * dev::kNT * 16 + 512;  // the kernel's re-tile buffer and LUT
+        res = (size_t)std::max<int64_t>(0, (int64_t)lds_cu / (mix_wgs + 1) + 1024 - own);
+      }
+      const dim3 gridm((unsigned)div_up(nchunks, 192 * (dev::kNT / 64)), (unsigned)(y1 - y0));
+      if (ntm) dev::k_colormix<true><<<gridm, dev::kNT, res, s>>>(a, nchunks, b_lo);
+      else dev::k_colormix<false><<<gridm, dev::kNT, res, s>>>(a, nchunks, b_lo);
+    } else if (p.cin == p.cout && !gray) {
       // byte-wise: flat 16-byte groups from the left margin to the right one
       const int C = p.cin;
       const int gb0 = -(int)div_up(px * C, 16);

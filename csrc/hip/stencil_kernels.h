@@ -49,14 +49,6 @@ constexpr int kW = 64;               // lanes per wave (one tile)
 constexpr int kWaves = kNT / kW;     // independent wave tiles per workgroup
 constexpr int kOutChunks = kW - 2;   // output chunks per wave tile
 
-// Orders this wave's LDS writes before its later LDS reads of other lanes' data
-// (LDS ops of one wave execute in order; this only stops compiler reordering).
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct WaveTask {
   int wave;   // wave index within the workgroup (scalar)
   int lane;

@@ -16,20 +16,25 @@
 
 namespace stripe {
 
-// out = expand?( post( gray?( pre(p) ) ) )  -- all per-byte LUTs are exact u8 maps
+// out = expand?( post( (gray | cmat)?( pre(p) ) ) )  -- all per-byte LUTs are exact
+// u8 maps; cmat is a 3 -> 3 colour matrix (filters.h) in the slot gray has, and a
+// program holds at most one of the two
 struct PointwiseProgram {
   bool has_pre = false;
   std::array<uint8_t, 256> pre{};
   bool gray = false;
   GrayMode gmode = GrayMode::BT601;
+  bool cmat = false;
+  std::array<int, 12> cm{};  // Op::cm: q row-major, then qb
   bool has_post = false;
   std::array<uint8_t, 256> post{};
   bool expand = false;
 
-  bool identity() const { return !has_pre && !gray && !has_post && !expand; }
-  bool lut_only() const { return !gray && !expand && !has_pre; }
-  // Prologue of a stencil pass may gray-convert and LUT, but not pre-LUT or expand.
-  bool prologue_ok() const { return !has_pre && !expand; }
+  bool identity() const { return !has_pre && !gray && !cmat && !has_post && !expand; }
+  bool lut_only() const { return !gray && !cmat && !expand && !has_pre; }
+  // Prologue of a stencil pass may gray-convert and LUT, but not pre-LUT, expand
+  // or mix channels (a colour matrix always runs as a pointwise pass of its own).
+  bool prologue_ok() const { return !has_pre && !expand && !cmat; }
   int channels_out(int cin) const { return expand ? 3 : (gray ? 1 : cin); }
   uint8_t apply_channel_lut(uint8_t v) const;  // post(pre(v)) when no gray
 };

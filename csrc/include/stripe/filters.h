@@ -15,6 +15,11 @@
 // with @constant the zeros outside the frame take part, so erode3@constant
 // darkens the frame edge - unlike OpenCV's morphology default, which ignores
 // them); open3/5 = erode,dilate and close3/5 = dilate,erode are parser sugar.
+// Colour matrices (colormatrix:..., sepia, saturation:S, swaprb, ycbcr[:inv]):
+// a 3x3 matrix and an offset on the (R, G, B) pixel in Q12 fixed point,
+//   out_c = sat_u8((sum_k q[c][k] * p_k + qb[c] + 2048) >> 12)   (>>: floor)
+// with q = nearbyint(m * 4096) and qb = nearbyint(b * 4096) (double, ties to
+// even), |q| <= 32767 (|m| < 8) and |b| <= 2048: every sum fits 27 bits.
 #pragma once
 
 #include <string>
@@ -33,6 +38,7 @@ enum class OpKind : int {
   Expand,   // 1 -> 3 channels (GRAY2BGR, kernel.cu:210)
   Stencil,  // integer stencil with compile-time coefficients (stencil_defs.h)
   Conv,     // float KxK convolution (blur:K, conv:...), MFMA path on GPU
+  ColorMatrix,  // 3 -> 3 channels: out_c = sat((sum_k q[c][k] p_k + qb[c] + 2048) >> 12)
 };
 
 enum class GrayMode : int { BT601 = 0, Ref = 1 };
@@ -88,6 +94,7 @@ struct Op {
   float fval = 0.f;  // contrast factor
   int ival = 0;      // brightness delta / threshold
   StencilId sid = StencilId::Gaussian5;
+  int cm[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // colour matrix: q row-major, then qb (kColorShift)
   int K = 0;                  // conv window
   std::vector<float> weights; // conv: K*K f32 weights
   std::vector<float> sep_h, sep_v;  // conv: 1-D factors when weights[dy][dx] = sep_v[dy] * sep_h[dx]
@@ -107,6 +114,14 @@ struct Op {
 // Parse "gray:ref,contrast:3.5,emboss3" (also presets "ref-gpu", "ref-cpu").
 std::vector<Op> parse_chain(const std::string& spec);
 std::string chain_to_string(const std::vector<Op>& ops);
+
+// Colour matrix arithmetic (the one definition every layer mirrors).
+constexpr int kColorShift = 12;
+inline uint8_t color_matrix_channel(const int* cm, int c, int r, int g, int b) {
+  const int v = (cm[3 * c] * r + cm[3 * c + 1] * g + cm[3 * c + 2] * b + cm[9 + c] + (1 << (kColorShift - 1))) >>
+                kColorShift;  // arithmetic shift: floor
+  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
 
 // Gaussian weights exactly as specified for blur:K (OpenCV getGaussianKernel sigma rule).
 std::vector<double> gaussian_1d(int K, double sigma);

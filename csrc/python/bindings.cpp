@@ -146,7 +146,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("pointwise_lut", [](const std::string& op) {
     auto ops = parse_chain(op);
     STRIPE_CHECK(ops.size() == 1 && ops[0].pointwise() && ops[0].kind != OpKind::Gray &&
-                     ops[0].kind != OpKind::Expand,
+                     ops[0].kind != OpKind::Expand && ops[0].kind != OpKind::ColorMatrix,
                  "pointwise_lut needs one per-channel op");
     std::vector<int> lut(256);
     for (int v = 0; v < 256; ++v) lut[v] = apply_pointwise_u8(ops[0], (uint8_t)v);
@@ -165,6 +165,18 @@ PYBIND11_MODULE(_C, m) {
     d["rank"] = rank_name(s.rank);  // "none" | "min" | "max" | "median" (rank filters: w empty)
     return d;
   });
+  m.def("color_matrix", [](const std::string& token) {
+    // the quantised matrix of one colour token (colormatrix:..., sepia, ...), for the tests
+    auto ops = parse_chain(token);
+    STRIPE_CHECK(ops.size() == 1 && ops[0].kind == OpKind::ColorMatrix, "color_matrix needs one colour matrix token");
+    py::dict d;
+    py::list q;
+    for (int c = 0; c < 3; ++c) q.append(std::vector<int>(ops[0].cm + 3 * c, ops[0].cm + 3 * c + 3));
+    d["q"] = q;
+    d["b"] = std::vector<int>(ops[0].cm + 9, ops[0].cm + 12);
+    d["shift"] = kColorShift;
+    return d;
+  }, "Q12 coefficients of a colour matrix token: out_c = sat((sum_k q[c][k] p_k + b[c] + 2048) >> 12)");
   m.def("rank_network", [](int K) {
     // the median networks of rank_net.h as (i, j, mode) steps, for the tests
     STRIPE_CHECK(K == 3 || K == 5, "rank networks exist for K = 3 and 5");
@@ -209,6 +221,7 @@ PYBIND11_MODULE(_C, m) {
       q["epi_lut"] = ps.has_epi;
       q["epi_expand"] = ps.epi_expand;
       q["out_margin_px"] = ps.out_margin_px;
+      q["cmat"] = ps.pro.cmat;
       passes.append(q);
     }
     d["passes"] = passes;

@@ -35,6 +35,12 @@ FILTERS = {
     "brightness:D": "sat(p + D)",
     "threshold:T": "p >= T ? 255 : 0",
     "expand": "gray -> 3 identical channels (GRAY2BGR, kernel.cu:210)",
+    # colour matrices (3 -> 3 channels, Q12 fixed point: sat((q.p + qb + 2048) >> 12))
+    "colormatrix:m00;m01;..;m22[:b0;b1;b2]": "out_c = sum_k m[c][k] in_k + b_c on (R, G, B), row-major; |m| < 8, |b| <= 2048",
+    "sepia": "the sepia tone matrix [[.393,.769,.189],[.349,.686,.168],[.272,.534,.131]]",
+    "saturation:S (saturate:S)": "mix with the BT.601 luma: 0 = gray, 1 = identity, > 1 = more colour; gray pixels stay",
+    "swaprb (bgr)": "swap the R and B channels (RGB <-> BGR)",
+    "ycbcr / ycbcr:inv": "JFIF full-range RGB -> (Y, Cb, Cr) and back",
     # stencils
     "emboss3 / emboss5": "kernel.cu:64-94 filters (3x3 and diagonal 5x5)",
     "gaussian3/5/7": "binomial Gaussian, integer, rounded",
@@ -237,6 +243,41 @@ def sep_conv2d(x, h, v, border: str = "reflect101"):
     return apply(x, f"sepconv:{K}:{hs}:{vs}", border)
 
 
+def color_matrix(x, M, offset=None):
+    """3x3 colour matrix (and optional 3 offsets) on an RGB image: out_c = sum_k M[c][k] in_k + offset_c,
+    evaluated in Q12 fixed point (`C.color_matrix(token)` shows the quantised coefficients)."""
+    m = np.asarray(M, dtype=np.float64)
+    if m.shape != (3, 3):
+        raise ValueError("M must be a 3x3 matrix")
+    spec = ";".join(repr(float(v)) for v in m.reshape(-1))
+    if offset is not None:
+        b = np.asarray(offset, dtype=np.float64).reshape(-1)
+        if b.shape != (3,):
+            raise ValueError("offset must have 3 entries")
+        spec += ":" + ";".join(repr(float(v)) for v in b)
+    return apply(x, f"colormatrix:{spec}")
+
+
+def sepia(x):
+    return apply(x, "sepia")
+
+
+def saturation(x, s: float):
+    return apply(x, f"saturation:{float(s)!r}")
+
+
+def swap_rb(x):
+    return apply(x, "swaprb")
+
+
+def rgb_to_ycbcr(x):
+    return apply(x, "ycbcr")
+
+
+def ycbcr_to_rgb(x):
+    return apply(x, "ycbcr:inv")
+
+
 def large_blur(x, ksize: int = 31, sigma: float = 0.0, border: str = "reflect101"):
     return apply(x, f"blur:{ksize}:{sigma}" if sigma > 0 else f"blur:{ksize}", border)
 
@@ -250,4 +291,5 @@ __all__ = [
     "FILTERS", "apply", "reference", "grayscale", "contrast", "invert", "brightness", "threshold",
     "gaussian_blur", "box_blur", "sobel", "sharpen", "laplace", "emboss",
     "median", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
+    "color_matrix", "sepia", "saturation", "swap_rb", "rgb_to_ycbcr", "ycbcr_to_rgb",
 ]
