@@ -626,32 +626,12 @@ static int64_t resident_simds() {
 
 void launch_blur_sep(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   STRIPE_CHECK(pc.conv != nullptr, "blur pass constants not prepared");
-  STRIPE_CHECK(L.in_base && L.out_base, "blur launch needs the allocation view (in_base/out_base)");
-  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_bytes > 0 &&
-                   L.out_bytes < (int64_t)dev::kOOB - 65536,
-               "stripe buffers must be < 2 GiB - 64 KiB for buffer-descriptor addressing");
-  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
-               "bad origin offsets");
+  static constexpr dev::ViewCheck kBlurView = {
+      nullptr, "blur launch needs the allocation view (in_base/out_base)",
+      "stripe buffers must be < 2 GiB - 64 KiB for buffer-descriptor addressing", 65536};
   dev::SepArgs sa{};
   dev::KArgs& a = sa.a;
-  a.in = L.in;
-  a.out = L.out;
-  a.zero_row = L.zero_row;
-  a.in_pitch = L.in_pitch;
-  a.out_pitch = L.out_pitch;
-  a.W = L.W;
-  a.E = L.W * p.cmid;
-  a.rows = L.rows;
-  a.row0 = L.row0;
-  a.Hg = L.Hg;
-  a.border = (int)p.border;
-  a.in_base = L.in_base;
-  a.out_base = L.out_base;
-  a.in_bytes = (uint32_t)L.in_bytes;
-  a.in_org = (uint32_t)L.in_org;
-  a.in_zero = (uint32_t)L.in_zero;
-  a.out_bytes = (uint32_t)L.out_bytes;
-  a.out_org = (uint32_t)L.out_org;
+  const auto [n0, n1, tiles_unused] = dev::fill_tile_args(p, L, a, &kBlurView);
   sa.R = p.R;
   sa.L = 16 * p.cmid;
   // kernel configuration: x-tiles per strip, pairs prefetched ahead, waves per
@@ -717,10 +697,7 @@ void launch_blur_sep(const Pass& p, const PassConsts& pc, const PassLaunch& L, h
       {STRIPE_BLUR_CFGW(3, false, 2, 2, 2, true, 8), STRIPE_BLUR_CFGW(3, false, 2, 2, 2, true, 4),
        STRIPE_BLUR_CFGW(3, false, 2, 1, 2, true, 4), STRIPE_BLUR_LATE(true)}};
 #undef STRIPE_BLUR_LATE
-  static const int env_variant = [] {
-    const char* e = std::getenv("STRIPE_BLUR_VARIANT");
-    return e ? std::atoi(e) : 0;
-  }();
+  const int env_variant = policy::blur_variant();
   const Cfg& cf = (p.cmid == 3 && !edge && env_variant > 0 && env_variant < 4) ? variants[lsb][env_variant]
                                                                                : cfgs[lsb][p.cmid == 3][edge];
 #undef STRIPE_BLUR_CFG
@@ -729,13 +706,7 @@ void launch_blur_sep(const Pass& p, const PassConsts& pc, const PassLaunch& L, h
   sa.nstrips = (int)div_up(L.W, 16 * cf.nx);
   const int64_t nstrips_w = div_up(sa.nstrips, cf.nw) * cf.nw;
 
-  const int n0 = std::max(0, L.ry[1] - L.ry[0]);
-  const int n1 = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
   if (n0 + n1 > 0) {
-    a.ry0 = L.ry[0];
-    a.ry1 = L.ry[0] + n0;
-    a.ry2 = n1 ? L.ry[2] : 0;
-    a.ry3 = n1 ? L.ry[3] : 0;
     // band = gpb 32-row groups.  A task costs gpb + 1 pair steps (one warm-up
     // pair per band), and the launch runs in rounds of one task per resident
     // wave slot (2 waves per SIMD): pick gpb minimising rounds x (gpb + 1).
@@ -767,14 +738,9 @@ void launch_blur_sep(const Pass& p, const PassConsts& pc, const PassLaunch& L, h
     // N=8 stripe): neighbouring windows' shared columns become L2 hits (lsb
     // 16384x2048 RGB 0.0454-0.046 -> 0.0431 ms, exact unchanged; a frame
     // streaming from HBM gains nothing, r3_blur_band2.sh); STRIPE_XCD forces it
-    static const int env_xcd = [] {
-      const char* e = std::getenv("STRIPE_XCD");
-      return e ? std::atoi(e) : -1;
-    }();
-    const int64_t pass_bytes = (int64_t)(n0 + n1) * L.W * 2 * p.cmid;
-    // (the engine's memory policy decides for a cache-cold stripe: L.nt = 1)
-    const bool streaming = L.nt >= 0 ? L.nt != 0 : pass_bytes > dev::kNtMinBytes;
-    a.nxcd = env_xcd >= 0 ? env_xcd : (streaming ? 0 : dev::kXcdCount);
+    const policy::StreamPolicy sp = policy::stream_policy(dev::policy_in(policy::Family::Blur, p, L, n0 + n1));
+    const bool streaming = sp.streaming;
+    a.nxcd = sp.nxcd;
     a.nb0 = (int)div_up(a.ry1 - sa.a0, band);
     a.nbands = a.nb0 + (n1 ? (int)div_up(a.ry3 - sa.a2, band) : 0);
     const dim3 grid((unsigned)(cf.nw == 1 ? div_up((int64_t)sa.nstrips * a.nbands, dev::kSepWaves)

@@ -607,15 +607,7 @@ static int conv_pairs(int K) {
 // B fragments: pair p, k-step s, part hl, lane l (g = l >> 4, n = l & 15),
 // element j: k = 32 s + 8 g + j -> (kernel row 2p + (k >= 48), window pixel
 // k mod 48); B[k][n] = w[ky][px - n] for 0 <= px - n < K, else 0.
-// STRIPE_CONV_F16=1: the f16 hi+lo kernel (k_conv_mfma) instead of the i8
-// weight-digit kernel (A/B runs)
-static bool conv_f16() {
-  static const bool v = [] {
-    const char* e = std::getenv("STRIPE_CONV_F16");
-    return e && std::atoi(e) != 0;
-  }();
-  return v;
-}
+using policy::conv_f16;  // STRIPE_CONV_F16 (launch_policy.h)
 
 // 4-row quads of a K x K window, padded to an even count (zero-weight quad).
 static int conv_quads(int K) {
@@ -763,73 +755,32 @@ void launch_conv_mfma(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
   STRIPE_CHECK(pc.conv != nullptr, "conv pass constants not prepared");
   STRIPE_CHECK(p.cmid == 1 || p.cmid == 3, "MFMA conv supports 1 or 3 channels");
   STRIPE_CHECK(p.K >= 1 && p.K <= 33 && p.R * p.cmid <= kMarginBytes, "MFMA conv window too large");
-  STRIPE_CHECK(L.in_base && L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_base && L.out_bytes > 0 &&
-                   L.out_bytes < (int64_t)dev::kOOB,
-               "conv launch needs the allocation view (< 2 GiB buffers)");
-  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
-               "bad origin offsets");
+  static constexpr dev::ViewCheck kConvView = {nullptr, "conv launch needs the allocation view (< 2 GiB buffers)",
+                                               "conv launch needs the allocation view (< 2 GiB buffers)"};
   if (pc.conv_mode == 1 || pc.conv_mode == 2) {
     const int nd = pc.conv_mode == 2 ? 2 : 3;
     dev::ConvI8Args ci{};
     dev::KArgs& a = ci.a;
-    a.in = L.in;
-    a.out = L.out;
-    a.zero_row = L.zero_row;
-    a.in_pitch = L.in_pitch;
-    a.out_pitch = L.out_pitch;
-    a.W = L.W;
-    a.E = L.W * p.cmid;
-    a.rows = L.rows;
-    a.row0 = L.row0;
-    a.Hg = L.Hg;
-    a.border = (int)p.border;
-    a.in_base = L.in_base;
-    a.in_bytes = (uint32_t)L.in_bytes;
-    a.in_org = (uint32_t)L.in_org;
-    a.in_zero = (uint32_t)L.in_zero;
-    a.out_base = L.out_base;
-    a.out_bytes = (uint32_t)L.out_bytes;
-    a.out_org = (uint32_t)L.out_org;
+    dev::fill_tile_args(p, L, a, &kConvView);
     ci.tw = reinterpret_cast<const dev::i32x4*>(pc.conv);
     ci.K = p.K;
     ci.R = p.R;
     ci.nq = conv_quads(p.K);
-    static const int env_split = [] {  // STRIPE_CONV_SPLIT=1: two-part epilogue at every K (A/B)
-      const char* e = std::getenv("STRIPE_CONV_SPLIT");
-      return e && std::atoi(e) == 1 ? 1 : 0;
-    }();
-    ci.split = env_split;
+    ci.split = policy::conv_split();
     ci.scale = pc.conv_scale;
     ci.bias = pc.conv_bias;
-    // m-tiles per wave (STRIPE_CONV_MT overrides for A/B runs)
-    static const int env_mt = [] {
-      const char* e = std::getenv("STRIPE_CONV_MT");
-      return e ? std::atoi(e) : 0;
-    }();
+    // m-tiles per wave and output tiles per workgroup (1 or 4); the knobs
+    // STRIPE_CONV_MT / STRIPE_CONV_NT / STRIPE_CONV_A1: launch_policy.h
     int mt = p.cmid == 3 ? dev::convq_mt<3>(nd) : dev::convq_mt<1>(nd);
-    if (env_mt > 0) mt = env_mt;
-    // output tiles per workgroup: 1, or 4 with STRIPE_CONV_NT=4 (the next
-    // tile's staging under the current tile's MFMAs, k_conv_i8 NT).  Measured
-    // on 16K RGB conv:31 (profiles/r5/conv/): 4 tiles at 2 m-tiles 2.32-2.36 ms
-    // exact / 1.85 ms lsb against 2.09-2.10 / 1.54-1.55 ms for one tile at 3
-    // m-tiles (4 tiles at 3 m-tiles spill): one tile stays the default
-    static const int env_nt = [] {
-      const char* e = std::getenv("STRIPE_CONV_NT");
-      return e ? std::atoi(e) : 0;
-    }();
-    const int nt = env_nt >= 4 ? 4 : 1;
+    if (policy::conv_mt() > 0) mt = policy::conv_mt();
+    const int nt = policy::conv_nt() >= 4 ? 4 : 1;
     using KFn = void (*)(dev::ConvI8Args);
     KFn fn = nullptr;
     size_t lds = 0;
     // (multi-tile instances only where they stay spill-free: RGB at 2
     // m-tiles, gray at 4 or 6)
     if (nt == 4) mt = p.cmid == 3 ? 2 : std::min(mt, 6);
-    // single-buffered A fragments (k_conv_i8 A1) wherever an instance exists;
-    // STRIPE_CONV_A1=0 for A/B runs against the double-buffered kernels
-    static const bool env_a1 = [] {
-      const char* e = std::getenv("STRIPE_CONV_A1");
-      return !(e && std::atoi(e) == 0);
-    }();
+    const bool env_a1 = policy::conv_a1();
     auto pick = [&]() {
       if (env_a1 && nt == 1) {
 #define STRIPE_CONVQ1(CC, MM, DD)                                                                            \
@@ -873,24 +824,7 @@ void launch_conv_mfma(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
   }
   dev::ConvArgs ca{};
   dev::KArgs& a = ca.a;
-  a.in = L.in;
-  a.out = L.out;
-  a.zero_row = L.zero_row;
-  a.in_pitch = L.in_pitch;
-  a.out_pitch = L.out_pitch;
-  a.W = L.W;
-  a.E = L.W * p.cmid;
-  a.rows = L.rows;
-  a.row0 = L.row0;
-  a.Hg = L.Hg;
-  a.border = (int)p.border;
-  a.in_base = L.in_base;
-  a.in_bytes = (uint32_t)L.in_bytes;
-  a.in_org = (uint32_t)L.in_org;
-  a.in_zero = (uint32_t)L.in_zero;
-  a.out_base = L.out_base;
-  a.out_bytes = (uint32_t)L.out_bytes;
-  a.out_org = (uint32_t)L.out_org;
+  dev::fill_tile_args(p, L, a, &kConvView);
   ca.tw = reinterpret_cast<const dev::half8*>(pc.conv);
   ca.K = p.K;
   ca.R = p.R;

@@ -5,7 +5,9 @@
 
 #include <cstdint>
 
+#include "launch_policy.h"
 #include "stripe/common.h"
+#include "stripe/kernels.h"
 
 namespace stripe {
 namespace dev {
@@ -62,14 +64,9 @@ constexpr uint32_t kOOB = 0x80000000u;  // lane offset bias that fails the range
 // 2 = nt, 16 = sc1).  Loads keep the default policy: halo rows are re-read by
 // the neighbouring band (nt loads measured 12-15 % slower on a 16K RGB frame).
 // Stores use nt when a pass streams more than the 256 MiB Infinity Cache
-// (launch_stencil picks the kernel instance).
+// (launch_policy.h decides; the launcher picks the kernel instance).
 constexpr int kLoadAux = 0;
 constexpr int kNtAux = 2;
-constexpr int64_t kNtMinBytes = 224ll << 20;
-// resident workgroups per CU of nt-store (HBM-streaming) stencil launches
-constexpr int kNtWgsSep = 2;     // separable (k_sep)
-constexpr int kNtWgsDirect = 3;  // direct (k_direct) without a gray prologue
-constexpr int kXcdCount = 8;  // MI355X: 8 XCDs of 32 CUs, one L2 each
 
 __device__ __forceinline__ int border_index_dev(int i, int n, int b) {
   if (i >= 0 && i < n) return i;
@@ -178,6 +175,40 @@ __device__ __forceinline__ void lut16(const uint8_t* lut, uint32_t (&o)[4]) {
     const uint32_t w = o[q];
     o[q] = pack4(lut[w & 0xFF], lut[(w >> 8) & 0xFF], lut[(w >> 16) & 0xFF], lut[w >> 24]);
   }
+}
+
+// ---- host side ----
+// The part of the argument block every launch fills the same way: geometry,
+// border, the buffer-descriptor view (checked) and the output row ranges.
+// n0 / n1: rows of the two ranges; tiles: wave tiles per row.
+struct TileLaunch {
+  int n0, n1, tiles;
+};
+// The allocation-view check as one launcher words it.
+struct ViewCheck {
+  const char* channels;    // cmid not 1 or 3 (nullptr: the caller has checked)
+  const char* need_view;   // in_base / out_base missing
+  const char* too_big;     // a view of 2 GiB or more
+  int64_t out_slack = 0;   // bytes the output view must stay below 2 GiB by
+};
+// view == nullptr (pointwise passes: plain pointers, E = W * cout, one launch
+// per row range): only the pointers, pitches, W and E are filled.
+// Defined in stencil.hip.
+TileLaunch fill_tile_args(const Pass& p, const PassLaunch& L, KArgs& a, const ViewCheck* view);
+
+// What policy::stream_policy asks about a launch of `rows` output rows.
+inline policy::PolicyIn policy_in(policy::Family f, const Pass& p, const PassLaunch& L, int rows) {
+  policy::PolicyIn in{f};
+  in.cin = p.cin;
+  in.cout = p.cout;
+  in.cmid = p.cmid;
+  in.W = L.W;
+  in.rows = rows;
+  in.nt = L.nt;
+  in.wgs = L.wgs;
+  in.gray_prologue = p.pro.gray;
+  in.lut_stage = p.pro.has_pre || p.pro.has_post;
+  return in;
 }
 
 }  // namespace dev

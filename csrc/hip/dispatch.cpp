@@ -4,26 +4,36 @@
 #include "stripe/kernels.h"
 
 #include <algorithm>
-#include <cstdlib>
+#include <map>
+#include <mutex>
+#include <tuple>
 
+#include "launch_policy.h"
 #include "stripe/common.h"
 
 namespace stripe {
 
+size_t nt_lds_reserve(const void* fn, int target) {
+  if (target <= 0) return 0;
+  static std::mutex mu;
+  static std::map<std::tuple<const void*, int, int>, size_t> cache;
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find({fn, dev, target});
+  if (it != cache.end()) return it->second;
+  int lds_cu = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+  hipFuncAttributes fa{};
+  HIP_CHECK(hipFuncGetAttributes(&fa, fn));
+  const size_t dyn = (size_t)policy::lds_reserve_bytes(lds_cu, (int64_t)fa.sharedSizeBytes, target);
+  cache[{fn, dev, target}] = dyn;
+  return dyn;
+}
+
 namespace {
 
-// Byte range of one buffer-descriptor view: the stencil / conv kernels address
-// rows with 32-bit offsets and bias masked lanes by 2^31 (dev::kOOB), so a view
-// must stay below 2 GiB (minus slack for the bias arithmetic).
-// STRIPE_DESC_LIMIT (bytes) lowers it so tests can exercise the chunked path.
-int64_t desc_limit() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("STRIPE_DESC_LIMIT");
-    const int64_t def = (1ll << 31) - (1ll << 20);
-    return e ? std::max<int64_t>(1 << 16, std::min<int64_t>(def, std::atoll(e))) : def;
-  }();
-  return v;
-}
+using policy::desc_limit;
 
 int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 

@@ -18,6 +18,7 @@
 #include <mutex>
 #include <vector>
 
+#include "launch_policy.h"
 #include "stripe/image.h"
 #include "stripe/kernels.h"
 
@@ -407,14 +408,7 @@ unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per)
 }  // namespace
 
 namespace {
-// STRIPE_JPEG_PIN=0 keeps the pageable coefficient upload (A/B switch)
-bool pin_uploads() {
-  static const bool on = [] {
-    const char* e = std::getenv("STRIPE_JPEG_PIN");
-    return !(e && std::atoi(e) == 0);
-  }();
-  return on;
-}
+bool pin_uploads() { return policy::jpeg_pin(); }  // STRIPE_JPEG_PIN (launch_policy.h)
 }  // namespace
 
 namespace {

@@ -9,7 +9,6 @@
 // multiply-shift constants).  Margins are processed like pixels, so the output
 // keeps the x-border contract of the next stencil.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "dev_common.h"
@@ -499,14 +498,10 @@ void launch_copy_rows(uint8_t* dst, int64_t dpitch, const uint8_t* src, int64_t 
 }
 
 void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
+  using policy::Family;
   dev::KArgs a{};
-  a.in = L.in;
-  a.out = L.out;
+  const dev::TileLaunch t = dev::fill_tile_args(p, L, a, nullptr);
   a.luts = pc.luts;
-  a.in_pitch = L.in_pitch;
-  a.out_pitch = L.out_pitch;
-  a.W = L.W;
-  a.E = L.W * p.cout;
   a.out_border = (int)p.out_margin_border;
   a.has_pre = p.pro.has_pre;
   a.has_post = p.pro.has_post;
@@ -520,95 +515,40 @@ void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
   const int px = std::min(p.out_margin_px, kMaxRadius);
   const int g0 = px > 0 ? -1 : 0;  // one 16-pixel group of left margin
   const int ngroups = (int)div_up(L.W + px, 16) - g0;
-  const int n0_rows = std::max(0, L.ry[1] - L.ry[0]);
-  const int n1_rows = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
+  const bool gray = p.pro.gray;
+  // store policy and residency cap of the pass (launch_policy.h), by kernel family
+  const Family fam = p.pro.cmat                 ? Family::ColorMix
+                     : p.cin == p.cout && !gray ? Family::PointwiseFlat
+                                                : Family::PointwiseChan;
+  const policy::StreamPolicy sp = policy::stream_policy(dev::policy_in(fam, p, L, t.n0 + t.n1));
+  const bool nt = sp.nt_stores;
+  // the cap as an LDS reservation of the kernel that runs (0: no cap)
+  auto reserve = [&](auto fn) { return nt_lds_reserve((const void*)fn, sp.cap_applied ? sp.cap : 0); };
   for (int r = 0; r < L.nrange; ++r) {
     const int y0 = L.ry[2 * r], y1 = L.ry[2 * r + 1];
     if (y1 <= y0) continue;
     a.ry0 = y0;
     dim3 grid((unsigned)div_up(ngroups, dev::kNT), (unsigned)(y1 - y0));
-    const bool gray = p.pro.gray;
-    // nt stores when the pass streams more than the Infinity Cache (as the
-    // stencil kernels; a smaller set is read back from the cache by the next
-    // pass) and only for 1-channel output, where one store instruction covers
-    // 1 KiB contiguously: the 3-channel store pattern (16 B per lane at a 48 B
-    // stride) writes partial lines that nt sends to HBM unmerged (16K RGB
-    // invert 0.295 -> 0.322 ms with nt; 16K gray:ref 0.192 -> 0.184 ms)
-    bool nt = p.cout == 1 && (int64_t)(n0_rows + n1_rows) * L.W * (p.cin + p.cout) > dev::kNtMinBytes;
-    if (const char* e = std::getenv("STRIPE_NT")) nt = std::atoi(e) != 0;
-    // A/B knob, off: capping the resident workgroups of channel-changing passes
-    // (STRIPE_PWG_WGS, LDS reservation) only slows them - 16K gray:ref 0.187 ms
-    // uncapped, 0.212 at 4 per CU, 0.284 at 2 (profiles/r2d/pw_wgs_ab.txt)
-    static const int pwg_wgs = [] {
-      const char* e = std::getenv("STRIPE_PWG_WGS");
-      return e ? std::atoi(e) : 0;
-    }();
-    size_t resg = 0;
-    if (pwg_wgs > 0 && (int64_t)(n0_rows + n1_rows) * L.W * (p.cin + p.cout) > dev::kNtMinBytes) {
-      int dev = 0, lds_cu = 0;
-      HIP_CHECK(hipGetDevice(&dev));
-      HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-      resg = (size_t)lds_cu / (size_t)(pwg_wgs + 1) + 1024 - 512;
-    }
     auto go = [&](auto k_nt, auto k_t) {
-      if (nt) k_nt<<<grid, dev::kNT, resg, s>>>(a, ngroups, g0);
-      else k_t<<<grid, dev::kNT, resg, s>>>(a, ngroups, g0);
+      if (nt) k_nt<<<grid, dev::kNT, reserve(k_nt), s>>>(a, ngroups, g0);
+      else k_t<<<grid, dev::kNT, reserve(k_t), s>>>(a, ngroups, g0);
     };
     if (p.pro.cmat) {
       // colour matrix: the byte range of the 16-pixel groups above (48 bytes
       // each: 3 chunks) as a flat chunk stream, 192 chunks per wave
       STRIPE_CHECK(p.cin == 3 && p.cout == 3 && !gray && !p.pro.expand, "colour matrix pass must be 3->3 channels");
       const int nchunks = 3 * ngroups, b_lo = 48 * g0;
-      const bool big = (int64_t)(n0_rows + n1_rows) * L.W * 6 > dev::kNtMinBytes;
-      bool ntm = big;
-      if (const char* e = std::getenv("STRIPE_NT")) ntm = std::atoi(e) != 0;
-      // HBM-streaming launches: the residency cap of the flat passes below
-      // (STRIPE_PW_WGS; 0 = no cap).  Default 3 workgroups per CU for the bare
-      // matrix (16K RGB sepia 0.277 ms uncapped, 0.305 at 2, 0.269 at 3, 0.268
-      // at 4) and 6 with a LUT stage, whose LDS lookups need more waves in
-      // flight (invert,sepia,brightness:10: 0.411 at 2, 0.313 at 3, 0.292 at 4,
-      // 0.268 at 6, 0.271 uncapped; profiles/colormatrix/README.md)
-      static const int env_wgs = [] {
-        const char* e = std::getenv("STRIPE_PW_WGS");
-        return e ? std::atoi(e) : -1;
-      }();
-      const int mix_wgs = env_wgs >= 0 ? env_wgs : (p.pro.has_pre || p.pro.has_post ? 6 : 3);
-      size_t res = 0;
-      if (mix_wgs > 0 && big && ntm) {
-        int dev = 0, lds_cu = 0;
-        HIP_CHECK(hipGetDevice(&dev));
-        HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-        const int64_t own = 3 * dev::kNT * 16 + 512;  // the kernel's re-tile buffer and LUT
-        res = (size_t)std::max<int64_t>(0, (int64_t)lds_cu / (mix_wgs + 1) + 1024 - own);
-      }
       const dim3 gridm((unsigned)div_up(nchunks, 192 * (dev::kNT / 64)), (unsigned)(y1 - y0));
-      if (ntm) dev::k_colormix<true><<<gridm, dev::kNT, res, s>>>(a, nchunks, b_lo);
-      else dev::k_colormix<false><<<gridm, dev::kNT, res, s>>>(a, nchunks, b_lo);
+      if (nt) dev::k_colormix<true><<<gridm, dev::kNT, reserve(dev::k_colormix<true>), s>>>(a, nchunks, b_lo);
+      else dev::k_colormix<false><<<gridm, dev::kNT, reserve(dev::k_colormix<false>), s>>>(a, nchunks, b_lo);
     } else if (p.cin == p.cout && !gray) {
       // byte-wise: flat 16-byte groups from the left margin to the right one
       const int C = p.cin;
       const int gb0 = -(int)div_up(px * C, 16);
       const int ngb = (int)div_up((L.W + px) * C, 16) - gb0;
-      const bool ntf = (int64_t)(n0_rows + n1_rows) * L.W * 2 * C > dev::kNtMinBytes &&
-                       !(std::getenv("STRIPE_NT") && std::atoi(std::getenv("STRIPE_NT")) == 0);
       const dim3 gridf((unsigned)div_up(ngb, dev::kNT * dev::kFlatU), (unsigned)(y1 - y0));
-      // streaming flat passes: at most 3 resident workgroups per CU (an LDS
-      // reservation the kernel never touches; fewer concurrent streams against
-      // HBM: 16K RGB invert 0.287 -> 0.269 ms, brightness 0.290 -> 0.268,
-      // profiles/r2d/pw_wgs_ab.txt); STRIPE_PW_WGS overrides (0 = no cap)
-      static const int pw_wgs = [] {
-        const char* e = std::getenv("STRIPE_PW_WGS");
-        return e ? std::atoi(e) : 3;
-      }();
-      size_t res = 0;
-      if (pw_wgs > 0 && ntf) {
-        int dev = 0, lds_cu = 0;
-        HIP_CHECK(hipGetDevice(&dev));
-        HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-        res = (size_t)lds_cu / (size_t)(pw_wgs + 1) + 1024 - 512;  // minus the kernel's 512-byte LUT
-      }
-      if (ntf) dev::k_pointwise_flat<true><<<gridf, dev::kNT, res, s>>>(a, ngb, gb0, C);
-      else dev::k_pointwise_flat<false><<<gridf, dev::kNT, 0, s>>>(a, ngb, gb0, C);
+      if (nt) dev::k_pointwise_flat<true><<<gridf, dev::kNT, reserve(dev::k_pointwise_flat<true>), s>>>(a, ngb, gb0, C);
+      else dev::k_pointwise_flat<false><<<gridf, dev::kNT, reserve(dev::k_pointwise_flat<false>), s>>>(a, ngb, gb0, C);
     } else if (p.cin == 3 && p.cout == 1 && gray)
       go(dev::k_pointwise<3, 1, true, true>, dev::k_pointwise<3, 1, true, false>);
     else if (p.cin == 3 && p.cout == 3 && gray)

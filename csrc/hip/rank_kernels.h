@@ -126,11 +126,10 @@ __global__ __launch_bounds__(kNT, (F::K >= 5 ? 2 : 4)) void k_rank(KArgs a) {
 // Launch geometry and occupancy cap as for the direct family (plan_bands,
 // kNtWgsDirect on HBM-streaming launches without a gray prologue).
 template <int C, class F, int PRO, bool EXP>
-void launch_rank(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s) {
+void launch_rank(bool skip, const KArgs& a, const BandLaunch& B) {
   const KernelFn fns[4] = {k_rank<C, F, PRO, false, 0, EXP>, k_rank<C, F, PRO, false, kNtAux, EXP>,
                            k_rank<C, F, PRO, true, 0, EXP>, k_rank<C, F, PRO, true, kNtAux, EXP>};
-  launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R,
-               stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect), s);
+  launch_bands(fns[2 * skip + B.nt], a, B, F::R, band_cap(B, policy::Family::Rank, is_gray(PRO)));
 }
 
 }  // namespace dev

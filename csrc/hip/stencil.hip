@@ -1,8 +1,6 @@
 // Stencil pass launcher (launch_stencil) and the small-K VALU convolution.
 // The stencil kernels live in stencil_kernels.h and are instantiated per filter
 // group in stencil_inst_*.hip.
-#include <cstdlib>
-
 #include "stencil_kernels.h"
 
 namespace stripe {
@@ -112,29 +110,25 @@ __global__ __launch_bounds__(kNT, 2) void k_conv_small(ConvSmallArgs ca) {
 }
 
 
-}  // namespace dev
-
-namespace {
-// The part of the argument block every wave-tile launch fills the same way:
-// geometry, border, the buffer-descriptor view (checked) and the output row
-// ranges.  n0 / n1: rows of the two ranges; tiles: wave tiles per row.
-struct TileLaunch {
-  int n0, n1, tiles;
-};
-TileLaunch fill_tile_args(const Pass& p, const PassLaunch& L, dev::KArgs& a) {
-  STRIPE_CHECK(p.cmid == 1 || p.cmid == 3, "wave-tile launch: channels must be 1 or 3");
-  STRIPE_CHECK(L.in_base && L.out_base, "wave-tile launch needs the allocation view (in_base/out_base)");
-  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)dev::kOOB && L.out_bytes > 0 &&
-                   L.out_bytes < (int64_t)dev::kOOB,
-               "stripe buffers must be < 2 GiB for buffer-descriptor addressing");
-  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
-               "bad origin offsets");
+TileLaunch fill_tile_args(const Pass& p, const PassLaunch& L, KArgs& a, const ViewCheck* view) {
+  const policy::RowRanges r = policy::row_ranges(L.ry, L.nrange);
   a.in = L.in;
   a.out = L.out;
-  a.zero_row = L.zero_row;
   a.in_pitch = L.in_pitch;
   a.out_pitch = L.out_pitch;
   a.W = L.W;
+  if (!view) {
+    a.E = L.W * p.cout;
+    return {r.n0, r.n1, 0};
+  }
+  if (view->channels) STRIPE_CHECK(p.cmid == 1 || p.cmid == 3, view->channels);
+  STRIPE_CHECK(L.in_base && L.out_base, view->need_view);
+  STRIPE_CHECK(L.in_bytes > 0 && L.in_bytes < (int64_t)kOOB && L.out_bytes > 0 &&
+                   L.out_bytes < (int64_t)kOOB - view->out_slack,
+               view->too_big);
+  STRIPE_CHECK((L.rebased || (L.in_org >= kMarginBytes && L.out_org >= kMarginBytes)) && L.in_zero >= kMarginBytes,
+               "bad origin offsets");
+  a.zero_row = L.zero_row;
   a.E = L.W * p.cmid;
   a.rows = L.rows;
   a.row0 = L.row0;
@@ -147,19 +141,24 @@ TileLaunch fill_tile_args(const Pass& p, const PassLaunch& L, dev::KArgs& a) {
   a.in_zero = (uint32_t)L.in_zero;
   a.out_bytes = (uint32_t)L.out_bytes;
   a.out_org = (uint32_t)L.out_org;
-  const int n0 = std::max(0, L.ry[1] - L.ry[0]);
-  const int n1 = L.nrange > 1 ? std::max(0, L.ry[3] - L.ry[2]) : 0;
-  a.ry0 = L.ry[0];
-  a.ry1 = L.ry[0] + n0;
-  a.ry2 = n1 ? L.ry[2] : 0;
-  a.ry3 = n1 ? L.ry[3] : 0;
-  return {n0, n1, (int)div_up(a.E, dev::kOutChunks * 16)};
+  a.ry0 = r.ry0;
+  a.ry1 = r.ry1;
+  a.ry2 = r.ry2;
+  a.ry3 = r.ry3;
+  return {r.n0, r.n1, (int)div_up(a.E, kOutChunks * 16)};
 }
+
+}  // namespace dev
+
+namespace {
+constexpr dev::ViewCheck kTileView = {"wave-tile launch: channels must be 1 or 3",
+                                      "wave-tile launch needs the allocation view (in_base/out_base)",
+                                      "stripe buffers must be < 2 GiB for buffer-descriptor addressing"};
 }  // namespace
 
 void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   dev::KArgs a{};
-  const auto [n0, n1, tiles] = fill_tile_args(p, L, a);
+  const auto [n0, n1, tiles] = dev::fill_tile_args(p, L, a, &kTileView);
   a.luts = pc.luts;
   a.out_px = p.out_margin_px;
   a.out_border = (int)p.out_margin_border;
@@ -179,46 +178,17 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
   }
   STRIPE_CHECK(!(p.pro.gray && p.cin != 3), "gray prologue needs 3 input channels");
   if (n0 + n1 == 0) return;
-  const int band = L.band;
-  // Output stores bypass the caches (nt) when the pass streams more than the
-  // Infinity Cache holds: then the next pass cannot hit in it anyway (16K RGB
-  // frame: gaussian5 0.322 -> 0.319 ms, reference chain 0.239 -> 0.227 ms).  A
-  // smaller working set (the 16K x 2K stripe of an 8-GPU run, 8K^2 gray) keeps
-  // the default policy so the next iteration reads its input from the cache
-  // (8K^2 gray gaussian5: 0.030 ms default vs 0.034 ms nt).
-  // The size rule is only the default: the engine passes the policy it tuned
-  // (L.nt), and a cache-cold stripe (EngineConfig::cold: a stream of frames, or
-  // a working set evicted between steps) streams from HBM however small its
-  // pass is -- the data's temperature, not the pass size, is what matters.
-  const int64_t pass_bytes = (int64_t)(n0 + n1) * L.W * (p.cin + p.cout);
-  bool nt = L.nt >= 0 ? L.nt != 0 : pass_bytes > dev::kNtMinBytes;
-  if (const char* e = std::getenv("STRIPE_NT")) nt = std::atoi(e) != 0;  // A/B switch
-  // A pass that stays in the Infinity Cache is bound by L2 / fabric traffic: the
-  // XCD-contiguous workgroup remap turns the halo rows that vertically adjacent
-  // bands share into L2 hits (one N=8 stripe of the 16K RGB frame, gaussian5:
-  // 0.0394-0.0401 -> 0.0372 ms at 8-row bands, profiles/r2/xcd_remap_stripe.txt).
-  // A pass streaming from HBM gains nothing from it (round 1: FETCH_SIZE 1.40x ->
-  // 1.15x of ideal, time unchanged, profiles/fetch_xcd_bands_16k_r1.txt).
-  a.nxcd = nt ? 0 : dev::kXcdCount;
+  // store policy and workgroup order are the same for the four stencil
+  // families; the cap is taken where the kernel family is known (launch_one)
+  const policy::StreamPolicy sp = policy::stream_policy(dev::policy_in(policy::Family::Sep, p, L, n0 + n1));
+  a.nxcd = sp.nxcd;
+  const dev::BandLaunch B{tiles, n0, n1, L.band, sp.nt_stores, L.wgs, L.order, s};
   using namespace sdef;
   switch (p.sid) {
-    case StencilId::Emboss3: dev::launch_filter<Emboss3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Emboss5: dev::launch_filter<Emboss5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Sharpen: dev::launch_filter<Sharpen>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Laplace: dev::launch_filter<Laplace>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Sobel: dev::launch_filter<Sobel>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::SobelL2: dev::launch_filter<SobelL2>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Gaussian3: dev::launch_filter<Gaussian3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Gaussian5: dev::launch_filter<Gaussian5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Gaussian7: dev::launch_filter<Gaussian7>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Box3: dev::launch_filter<Box3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Box5: dev::launch_filter<Box5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Median3: dev::launch_filter<Median3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Median5: dev::launch_filter<Median5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Erode3: dev::launch_filter<Erode3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Erode5: dev::launch_filter<Erode5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Dilate3: dev::launch_filter<Dilate3>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
-    case StencilId::Dilate5: dev::launch_filter<Dilate5>(p, a, tiles, n0, n1, band, nt, L.wgs, s, L.order); break;
+#define STRIPE_LAUNCH_CASE(F) \
+  case StencilId::F: dev::launch_filter<F>(p, a, B); break;
+    STRIPE_STENCIL_FILTERS(STRIPE_LAUNCH_CASE)
+#undef STRIPE_LAUNCH_CASE
     default: fail("unknown stencil");
   }
   HIP_CHECK(hipGetLastError());
@@ -259,12 +229,12 @@ void launch_conv_small(const Pass& p, const PassLaunch& L, hipStream_t s) {
   STRIPE_CHECK(conv_small_supported(p), "conv pass not eligible for the direct VALU kernel");
   dev::ConvSmallArgs ca{};
   dev::KArgs& a = ca.a;
-  const auto [n0, n1, tiles] = fill_tile_args(p, L, a);
+  const auto [n0, n1, tiles] = dev::fill_tile_args(p, L, a, &kTileView);
   for (int i = 0; i < p.K * p.K; ++i) ca.w[i] = p.conv_w[(size_t)i];
   if (n0 + n1 == 0) return;
-  const int64_t pass_bytes = (int64_t)(n0 + n1) * L.W * 2 * p.cmid;
-  bool nt = pass_bytes > dev::kNtMinBytes;
-  if (const char* e = std::getenv("STRIPE_NT")) nt = std::atoi(e) != 0;
+  const policy::StreamPolicy sp = policy::stream_policy(dev::policy_in(policy::Family::ConvSmall, p, L, n0 + n1));
+  const bool nt = sp.nt_stores;
+  a.nxcd = sp.nxcd;
   using K = void (*)(dev::ConvSmallArgs);
   K fn = nullptr;
 #define STRIPE_CONV_SMALL(CC, KK)                                                                     \

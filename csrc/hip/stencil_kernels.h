@@ -31,15 +31,10 @@
 //     the y-border from a scalar row remap; edge waves rewrite the output margins
 //     after their band (one vmcnt(0) per band).
 
-#include <cstdlib>
-
 #include "dev_common.h"
 #include "stripe/kernels.h"
 #include "stripe/stencil_defs.h"
 
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
 
 namespace stripe {
@@ -1147,21 +1142,8 @@ __global__ __launch_bounds__(kNT, (F::K >= 5 ? 3 : 4)) void k_direct(KArgs a) {
 // at once in a compact window (measured on MI355X, 16384-wide RGB: gaussian5
 // 0.323 ms/pass at 12 rows vs 0.370 ms with one tall band per workgroup, which
 // spreads the concurrent streams over the whole frame); the engine's autotuner
-// can override per shape.
-// XCD-aware workgroup remap (xcd_remap): the caller sets a.nxcd (launch_stencil:
-// on for passes whose working set stays in the Infinity Cache, where halo rows
-// shared by vertically adjacent bands become L2 hits); STRIPE_XCD=<n> forces it
-// (0 = off) for A/B runs.
-inline int env_nxcd() {
-  static const int v = [] {
-    const char* e = std::getenv("STRIPE_XCD");
-    return e ? std::atoi(e) : -1;
-  }();
-  return v;
-}
-
+// can override per shape.  The caller sets a.nxcd (policy::stream_policy).
 inline void plan_bands(KArgs& a, dim3& grid, int tiles, int n0, int n1, int band, int R) {
-  if (env_nxcd() >= 0) a.nxcd = env_nxcd();
   if (band <= 0) band = R >= 3 ? 16 : 12;
   band = (int)align_up(band, 4);
   a.band = band;
@@ -1171,62 +1153,32 @@ inline void plan_bands(KArgs& a, dim3& grid, int tiles, int n0, int n1, int band
   grid = dim3((unsigned)div_up((int64_t)tiles * a.nbands, kWaves));
 }
 
-// Occupancy cap of the HBM-streaming (nt-store) stencil launches: fewer
-// resident waves per SIMD keep fewer concurrent row streams open against HBM
-// (16384^2 RGB, band autotune on, profiles/r2d/nt_wgs_ab.txt: separable
-// gaussian5 0.311 -> 0.282 ms at 2 workgroups per CU, gaussian3 0.299 -> 0.269,
-// sobel 0.315 -> 0.293; direct emboss3 0.300 -> 0.283 at 3; the gray-prologue
-// direct kernels read 3 bytes per output byte and gain nothing).  The cap is an
-// LDS reservation (dynamic shared memory the kernel never touches) sized so
-// only `target` workgroups fit a CU's LDS; STRIPE_NT_WGS overrides the cap of
-// HBM-streaming launches (stencil_cap; 0 = no cap).
-inline int env_nt_wgs() {
-  static const int env = [] {
-    const char* e = std::getenv("STRIPE_NT_WGS");
-    return e ? std::atoi(e) : -1;
-  }();
-  return env;
-}
-
-inline size_t nt_lds_reserve(const void* fn, int target) {
-  if (target <= 0) return 0;
-  static std::mutex mu;
-  static std::map<std::tuple<const void*, int, int>, size_t> cache;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({fn, dev, target});
-  if (it != cache.end()) return it->second;
-  int lds_cu = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-  hipFuncAttributes fa{};
-  HIP_CHECK(hipFuncGetAttributes(&fa, fn));
-  const size_t total = (size_t)lds_cu / (size_t)(target + 1) + 1024;  // target fit, target + 1 do not
-  const size_t dyn = total > fa.sharedSizeBytes ? total - fa.sharedSizeBytes : 0;
-  cache[{fn, dev, target}] = dyn;
-  return dyn;
-}
-
-// Occupancy cap of one launch: wgs >= 0 is the engine's choice (its autotuner
-// times the caps per pass and box, since the best cap depends on the clock
-// and memory behaviour of the box: round-2 driver run);
-// wgs < 0 takes the family default, applied to HBM-streaming launches only.
-inline int stencil_cap(bool nt, int wgs, int family_default) {
-  if (nt && env_nt_wgs() >= 0) return env_nt_wgs();  // A/B runs pin the streaming cap only
-  if (wgs >= 0) return wgs;
-  return nt ? family_default : 0;
-}
+// What launch_stencil decided for a pass, handed down the filter dispatch.
+struct BandLaunch {
+  int tiles;   // wave tiles per row
+  int n0, n1;  // rows of the two output ranges
+  int band;    // PassLaunch::band
+  bool nt;     // nt-store instances (policy::stream_policy)
+  int wgs;     // PassLaunch::wgs
+  int order;   // PassLaunch::order
+  hipStream_t s;
+};
 
 // Plans the bands of one launch (plan_bands) and starts fn over them with at
 // most `cap` workgroups per CU (nt_lds_reserve; 0 = no cap).  grid_of: the
 // grid for the planned bands where it is not plan_bands' own (kRuns).
 using KernelFn = void (*)(KArgs);
-inline void launch_bands(KernelFn fn, KArgs a, int tiles, int n0, int n1, int band, int R, int cap, hipStream_t s,
+inline void launch_bands(KernelFn fn, KArgs a, const BandLaunch& B, int R, int cap,
                          int64_t (*grid_of)(int ntx, int nbands) = nullptr) {
   dim3 grid;
-  plan_bands(a, grid, tiles, n0, n1, band, R);
-  if (grid_of) grid = dim3((unsigned)grid_of(tiles, a.nbands));
-  fn<<<grid, kNT, nt_lds_reserve((const void*)fn, cap), s>>>(a);
+  plan_bands(a, grid, B.tiles, B.n0, B.n1, B.band, R);
+  if (grid_of) grid = dim3((unsigned)grid_of(B.tiles, a.nbands));
+  fn<<<grid, kNT, nt_lds_reserve((const void*)fn, cap), B.s>>>(a);
+}
+
+// The cap of a stencil launch of family `f` (policy::stencil_cap).
+inline int band_cap(const BandLaunch& B, policy::Family f, bool gray_prologue = false) {
+  return policy::stencil_cap(B.nt, B.wgs, policy::stencil_cap_default(f, gray_prologue));
 }
 
 // Rank filters (sdef::RankDef: median / erode / dilate) have their own kernel
@@ -1241,47 +1193,30 @@ struct RankTag<F, std::void_t<decltype(F::RANK)>> {
   static constexpr int value = F::RANK;
 };
 template <int C, class F, int PRO, bool EXP>
-void launch_rank(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s);
+void launch_rank(bool skip, const KArgs& a, const BandLaunch& B);
 
+// B.order counts on the plain path only (sep_order_supported).
 template <int C, class F, int PRO, bool EXP = false>
-void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1, int band, hipStream_t s,
-                int order = 0) {
+void launch_one(bool skip, const KArgs& a, BandLaunch B) {
   using K = KernelFn;
+  using policy::Family;
+  const bool nt = B.nt;
   if constexpr (F::SEP && PRO == PRO_NONE && !EXP) {
     if constexpr (SepTraits<F>::SYM) {
-      if (order == 1) {  // kRuns (runs_task); the remap is its own
+      if (B.order == 1) {  // kRuns (runs_task); the remap is its own
         const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP, kRuns>, k_sep<C, F, PRO, false, kNtAux, EXP, kRuns>,
                           k_sep<C, F, PRO, true, 0, EXP, kRuns>, k_sep<C, F, PRO, true, kNtAux, EXP, kRuns>};
-        launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s,
-                     runs_grid);
+        launch_bands(fns[2 * skip + nt], a, B, F::R, band_cap(B, Family::Sep), runs_grid);
         return;
       }
     }
   }
   if constexpr (F::SEP && F::SOBEL && C == 1 && PRO == PRO_NONE && !EXP) {
     if constexpr (!F::L2) {
-      // gray L1 sobel on row pairs (STRIPE_SOBEL_RP=0: the k_sep form, A/B)
-      static const bool rp = [] {
-        const char* e = std::getenv("STRIPE_SOBEL_RP");
-        return !(e && std::atoi(e) == 0);
-      }();
-      // 8-row bands request all ten input rows up front (the autotuner's
-      // band-8 candidate; full 8192^2 frame 2-3.5 % faster than the best
-      // streamed band, profiles/r5/cfg3/README.md); STRIPE_SOBEL_PB=8|12
-      // forces bands of that height with up-front loads (A/B)
-      static const int pb_env = [] {
-        const char* e = std::getenv("STRIPE_SOBEL_PB");
-        const int v = e ? std::atoi(e) : -1;
-        return v == 0 || v == 8 || v == 12 ? v : -1;
-      }();
-      // 1 KiB tiles with edge loads (STRIPE_SOBEL_WIDE=0: 62-lane tiles, A/B)
-      static const bool wide = [] {
-        const char* e = std::getenv("STRIPE_SOBEL_WIDE");
-        return !(e && std::atoi(e) == 0);
-      }();
       // k_sobel_rp stores its sums as they are: an epilogue LUT takes the k_sep form
-      if (rp && !skip && !a.has_epi) {
-        const int pb = pb_env >= 0 ? pb_env : (band == 8 ? 8 : 0);
+      if (policy::sobel_rp() && !skip && !a.has_epi) {
+        const bool wide = policy::sobel_wide();
+        const int pb = policy::sobel_pb() >= 0 ? policy::sobel_pb() : (B.band == 8 ? 8 : 0);
         const K fns[2][3][2] = {{{k_sobel_rp<0>, k_sobel_rp<kNtAux>},
                                  {k_sobel_rp<0, 8>, k_sobel_rp<kNtAux, 8>},
                                  {k_sobel_rp<0, 12>, k_sobel_rp<kNtAux, 12>}},
@@ -1289,58 +1224,53 @@ void launch_one(bool skip, bool nt, int wgs, KArgs a, int tiles, int n0, int n1,
                                  {k_sobel_rp<0, 8, true>, k_sobel_rp<kNtAux, 8, true>},
                                  {k_sobel_rp<0, 12, true>, k_sobel_rp<kNtAux, 12, true>}}};
         const K fn = fns[wide][pb == 8 ? 1 : pb == 12 ? 2 : 0][nt];
-        if (pb) band = pb;
-        if (wide) tiles = (int)div_up((int64_t)a.E, kW * 16);
-        launch_bands(fn, a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s);
+        if (pb) B.band = pb;
+        if (wide) B.tiles = (int)div_up((int64_t)a.E, kW * 16);
+        launch_bands(fn, a, B, F::R, band_cap(B, Family::SobelRp));
         return;
       }
     }
   }
   if constexpr (RankTag<F>::value != 0) {
-    launch_rank<C, F, PRO, EXP>(skip, nt, wgs, a, tiles, n0, n1, band, s);
+    launch_rank<C, F, PRO, EXP>(skip, a, B);
   } else if constexpr (F::SEP) {
     const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP>, k_sep<C, F, PRO, false, kNtAux, EXP>,
                       k_sep<C, F, PRO, true, 0, EXP>, k_sep<C, F, PRO, true, kNtAux, EXP>};
-    launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R, stencil_cap(nt, wgs, kNtWgsSep), s);
+    launch_bands(fns[2 * skip + nt], a, B, F::R, band_cap(B, Family::Sep));
   } else {
     const K fns[4] = {k_direct<C, F, PRO, false, 0, EXP>, k_direct<C, F, PRO, false, kNtAux, EXP>,
                       k_direct<C, F, PRO, true, 0, EXP>, k_direct<C, F, PRO, true, kNtAux, EXP>};
-    launch_bands(fns[2 * skip + nt], a, tiles, n0, n1, band, F::R,
-                 stencil_cap(nt, wgs, is_gray(PRO) ? 0 : kNtWgsDirect), s);
+    launch_bands(fns[2 * skip + nt], a, B, F::R, band_cap(B, Family::Direct, is_gray(PRO)));
   }
 }
 
 template <int PRO, class F>
-void launch_gray_out(bool expand, bool skip, bool nt, int wgs, const KArgs& a, int tiles, int n0, int n1, int band,
-                     hipStream_t s) {
-  if (expand) launch_one<1, F, PRO, true>(skip, nt, wgs, a, tiles, n0, n1, band, s);
-  else launch_one<1, F, PRO, false>(skip, nt, wgs, a, tiles, n0, n1, band, s);
+void launch_gray_out(bool expand, bool skip, const KArgs& a, const BandLaunch& B) {
+  if (expand) launch_one<1, F, PRO, true>(skip, a, B);
+  else launch_one<1, F, PRO, false>(skip, a, B);
 }
 
 template <class F>
-void launch_filter(const Pass& p, const KArgs& a, int tiles, int n0, int n1, int band, bool nt, int wgs,
-                   hipStream_t s, int order) {
+void launch_filter(const Pass& p, const KArgs& a, const BandLaunch& B) {
   const bool gray = p.pro.gray;
   const bool lut = p.pro.has_post;
   const bool skip = p.border == Border::Skip;
   const bool ex = p.epi_expand;
   if (p.cmid == 3) {
     STRIPE_CHECK(!gray && !ex, "gray prologue / expand epilogue need a 1-channel stencil");
-    if (lut) launch_one<3, F, PRO_LUT>(skip, nt, wgs, a, tiles, n0, n1, band, s);
-    else launch_one<3, F, PRO_NONE>(skip, nt, wgs, a, tiles, n0, n1, band, s, order);
+    if (lut) launch_one<3, F, PRO_LUT>(skip, a, B);
+    else launch_one<3, F, PRO_NONE>(skip, a, B);
   } else {
-    if (gray && a.gmode == 1) launch_gray_out<PRO_GRAYLUT, F>(ex, skip, nt, wgs, a, tiles, n0, n1, band, s);
-    else if (gray) launch_gray_out<PRO_GRAY, F>(ex, skip, nt, wgs, a, tiles, n0, n1, band, s);
-    else if (lut) launch_gray_out<PRO_LUT, F>(ex, skip, nt, wgs, a, tiles, n0, n1, band, s);
-    else if (!ex) launch_one<1, F, PRO_NONE>(skip, nt, wgs, a, tiles, n0, n1, band, s, order);
-    else launch_gray_out<PRO_NONE, F>(ex, skip, nt, wgs, a, tiles, n0, n1, band, s);
+    if (gray && a.gmode == 1) launch_gray_out<PRO_GRAYLUT, F>(ex, skip, a, B);
+    else if (gray) launch_gray_out<PRO_GRAY, F>(ex, skip, a, B);
+    else if (lut) launch_gray_out<PRO_LUT, F>(ex, skip, a, B);
+    else launch_gray_out<PRO_NONE, F>(ex, skip, a, B);
   }
 }
 
 
 // Every filter F has launch_filter<F> compiled in exactly one stencil_inst_*.hip.
-#define STRIPE_LAUNCH_FILTER_SIG(F) \
-  void launch_filter<sdef::F>(const Pass&, const KArgs&, int, int, int, int, bool, int, hipStream_t, int)
+#define STRIPE_LAUNCH_FILTER_SIG(F) void launch_filter<sdef::F>(const Pass&, const KArgs&, const BandLaunch&)
 #define STRIPE_EXTERN_LAUNCH_FILTER(F) extern template STRIPE_LAUNCH_FILTER_SIG(F);
 #define STRIPE_INSTANTIATE_LAUNCH_FILTER(F) template STRIPE_LAUNCH_FILTER_SIG(F);
 #define STRIPE_STENCIL_FILTERS(X) \

@@ -75,6 +75,12 @@ struct PassLaunch {
   bool rebased = false;
 };
 
+// Occupancy cap as an LDS reservation: the dynamic shared memory (bytes) that
+// lets only `target` workgroups of kernel `fn` fit a CU's LDS on the current
+// device (policy::lds_reserve_bytes of the kernel's static LDS; 0 for
+// target <= 0).  Cached per kernel, device and target (dispatch.cpp).
+size_t nt_lds_reserve(const void* fn, int target);
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);

@@ -13,6 +13,7 @@
 
 #include <memory>
 
+#include "../hip/launch_policy.h"
 #include "stripe/chain.h"
 #include "stripe/comm.h"
 #include "stripe/engine.h"
@@ -227,6 +228,45 @@ PYBIND11_MODULE(_C, m) {
     d["passes"] = passes;
     return d;
   }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true);
+
+  // ---- launch policy (csrc/hip/launch_policy.h: pure host functions, no GPU) ----
+  m.def("launch_policy", [](const std::string& family, int cin, int cout, int cmid, int W, int rows, int nt, int wgs,
+                            bool gray_prologue, bool lut_stage) {
+    static const std::pair<const char*, policy::Family> names[] = {
+        {"sep", policy::Family::Sep},           {"sobel_rp", policy::Family::SobelRp},
+        {"direct", policy::Family::Direct},     {"rank", policy::Family::Rank},
+        {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
+        {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
+        {"blur", policy::Family::Blur}};
+    const policy::Family* f = nullptr;
+    for (const auto& n : names)
+      if (family == n.first) f = &n.second;
+    STRIPE_CHECK(f != nullptr, "unknown kernel family '" << family << "'");
+    policy::PolicyIn in{*f};
+    in.cin = cin;
+    in.cout = cout;
+    in.cmid = cmid;
+    in.W = W;
+    in.rows = rows;
+    in.nt = nt;
+    in.wgs = wgs;
+    in.gray_prologue = gray_prologue;
+    in.lut_stage = lut_stage;
+    const policy::StreamPolicy r = policy::stream_policy(in);
+    py::dict d;
+    d["nt_stores"] = r.nt_stores;
+    d["streaming"] = r.streaming;
+    d["nxcd"] = r.nxcd;
+    d["cap"] = r.cap;
+    d["cap_applied"] = r.cap_applied;
+    return d;
+  }, py::arg("family"), py::arg("cin") = 3, py::arg("cout") = 3, py::arg("cmid") = 3, py::arg("W") = 0,
+     py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
+     py::arg("lut_stage") = false,
+     "the launch decision of a kernel family: sep | sobel_rp | direct | rank | conv_small | pointwise | "
+     "pointwise_flat | colormix | blur");
+  m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
+        py::arg("target"));
 
   // ---- golden ----
   m.def("golden_apply", [](const U8Array& a, const std::string& chain, const std::string& border, bool fuse) {

@@ -6,6 +6,7 @@
 #include "stripe/trace.h"
 
 #include "engine_internal.h"
+#include "launch_policy.h"
 
 #include <algorithm>
 #include <chrono>
@@ -84,7 +85,7 @@ void Engine::autotune_bands() {
   // -1: the family default (separable 2 / direct 3 workgroups per CU on
   // HBM-streaming passes, none on cache-resident ones), 0: no cap
   const int caps[] = {-1, 0, 2, 3, 4};
-  const bool fixed_cap = std::getenv("STRIPE_NT_WGS") != nullptr;  // A/B runs pin the cap
+  const bool fixed_cap = policy::nt_wgs_knob().set;  // A/B runs pin the cap
   hipEvent_t e0 = ev_[6], e1 = ev_[7];
   // Cold tuning (EngineConfig::cold): a stripe whose steps all read from HBM
   // must not be tuned on data the previous candidate left in the 256 MiB

@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -43,6 +44,20 @@ using namespace stripe::dev;
       std::exit(1);                                                                       \
     }                                                                                     \
   } while (0)
+
+// This program links none of the library's units: the occupancy-cap
+// reservation of csrc/hip/dispatch.cpp for the one device and thread used here.
+size_t stripe::nt_lds_reserve(const void* fn, int target) {
+  static std::map<std::pair<const void*, int>, size_t> cache;
+  auto it = cache.find({fn, target});
+  if (it != cache.end()) return it->second;
+  int dev = 0, lds_cu = 0;
+  hipFuncAttributes fa{};
+  CK(hipGetDevice(&dev));
+  CK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
+  CK(hipFuncGetAttributes(&fa, fn));
+  return cache[{fn, target}] = (size_t)policy::lds_reserve_bytes(lds_cu, (int64_t)fa.sharedSizeBytes, target);
+}
 
 template <int AUX>
 __global__ __launch_bounds__(256) void k_copy_lin(const uint8_t* in, uint8_t* out, uint32_t bytes) {
