@@ -79,12 +79,34 @@ void normalize(PointwiseProgram& prog) {
       if (l[i] != i) return false;
     return true;
   };
-  if (prog.has_post && is_id(prog.post)) prog.has_post = false;
-  if (prog.has_pre && is_id(prog.pre)) prog.has_pre = false;
+  // the slot a statistic op's run-time table is composed into stays, whatever
+  // the static table holds: pre in front of a gray / matrix stage, else post
+  const bool stat_pre = prog.has_stat && (prog.gray || prog.cmat);
+  const bool stat_post = prog.has_stat && !stat_pre;
+  if (stat_pre && !prog.has_pre) {
+    prog.pre = identity_lut();
+    prog.has_pre = true;
+  }
+  if (stat_post && !prog.has_post) {
+    prog.post = identity_lut();
+    prog.has_post = true;
+  }
+  if (prog.has_post && !stat_post && is_id(prog.post)) prog.has_post = false;
+  if (prog.has_pre && !stat_pre && is_id(prog.pre)) prog.has_pre = false;
+}
+
+const char* stat_name(const Op& op) {
+  switch (op.stat) {
+    case StatKind::Equalize: return "equalize";
+    case StatKind::AutoContrast: return "autocontrast";
+    case StatKind::Otsu: return "otsu";
+  }
+  return "?";
 }
 
 std::string prog_desc(const PointwiseProgram& p) {
   std::string s;
+  if (p.has_stat) s += std::string("stat:") + stat_name(p.stat) + ",";
   if (p.has_pre) s += "lut,";
   if (p.gray) s += p.gmode == GrayMode::Ref ? "gray:ref," : "gray:bt601,";
   if (p.cmat) s += "cmat,";
@@ -130,9 +152,47 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     pending_cin = c;
   };
 
+  // pointwise ops with no stencil after them (the chain's tail, or the ops in
+  // front of a statistic op): epilogue of the last stencil if they are a LUT
+  // and/or an expand of its 1-channel result (the reference's gray -> emboss ->
+  // expand GPU chain, kernel.cu:192-196, is then one pass), else their own pass.
+  // A program that starts with a statistic op is never an epilogue: its
+  // histogram is of that pass's output.
+  auto flush_tail = [&]() {
+    normalize(pending);
+    if (pending.identity()) return;
+    Pass* last = plan.passes.empty() ? nullptr : &plan.passes.back();
+    const bool epi_ok = fuse && last && !pending.has_stat &&
+                        (last->kind == PassKind::Separable || last->kind == PassKind::Direct) &&
+                        !last->has_epi && !last->epi_expand && !pending.gray && !pending.cmat && !pending.has_pre &&
+                        (!pending.expand || last->cmid == 1);
+    if (epi_ok) {
+      if (pending.has_post) {
+        last->has_epi = true;
+        last->epi = pending.post;
+      }
+      if (pending.expand) {
+        last->epi_expand = true;
+        last->cout = 3;
+      }
+      last->desc += " epilogue[" + prog_desc(pending) + "]";
+      pending = PointwiseProgram{};
+      pending_cin = c;
+    } else {
+      flush_pointwise();
+    }
+  };
+
   for (const Op& op : ops) {
     if (op.pointwise()) {
       switch (op.kind) {
+        case OpKind::Stat:
+          // flush what is pending, then open a new run with the statistic op as
+          // its first stage: the histogram it needs is that of its pass's input
+          flush_tail();
+          pending.has_stat = true;
+          pending.stat = op;
+          break;
         case OpKind::Gray:
           if (c == 1) break;  // gray of gray is the identity
           // (a pending matrix is rounded and saturated: gray of it is a second stage)
@@ -172,8 +232,11 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     // a fused prologue cooks the raw zeros of the margins and of the rows
     // outside the frame: a program that moves the zero pixel (gray maps zero to
     // zero, so that is post[0] != 0) runs as a pass of its own, which zeroes
-    // its constant margins, and the stencil reads raw zeros
-    const bool moves_zero = p.border == Border::Constant && pending.has_post && pending.post[0] != 0;
+    // its constant margins, and the stencil reads raw zeros.  A run-time table
+    // (a statistic op) counts as moving the zero pixel: the plan's structure
+    // must not depend on table contents
+    const bool moves_zero =
+        p.border == Border::Constant && (pending.has_stat || (pending.has_post && pending.post[0] != 0));
     if (conv || !fuse || !pending.prologue_ok() || moves_zero) flush_pointwise();
     if (conv) {
       STRIPE_CHECK(p.border != Border::Skip, "skip border is only defined for integer stencils");
@@ -208,31 +271,7 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     pending = PointwiseProgram{};
     pending_cin = c;
   }
-  // trailing pointwise ops: epilogue of the last stencil if they are a LUT and/or
-  // an expand of its 1-channel result (the reference's gray -> emboss -> expand
-  // GPU chain, kernel.cu:192-196, is then one pass), else their own pass
-  normalize(pending);
-  if (!pending.identity()) {
-    Pass* last = plan.passes.empty() ? nullptr : &plan.passes.back();
-    const bool epi_ok = fuse && last &&
-                        (last->kind == PassKind::Separable || last->kind == PassKind::Direct) &&
-                        !last->has_epi && !last->epi_expand && !pending.gray && !pending.cmat && !pending.has_pre &&
-                        (!pending.expand || last->cmid == 1);
-    if (epi_ok) {
-      if (pending.has_post) {
-        last->has_epi = true;
-        last->epi = pending.post;
-      }
-      if (pending.expand) {
-        last->epi_expand = true;
-        last->cout = 3;
-      }
-      last->desc += " epilogue[" + prog_desc(pending) + "]";
-      pending = PointwiseProgram{};
-    } else {
-      flush_pointwise();
-    }
-  }
+  flush_tail();  // trailing pointwise ops
   if (plan.passes.empty()) {  // identity chain: keep one copy pass so outputs are fresh
     Pass p;
     p.kind = PassKind::Pointwise;
@@ -282,13 +321,28 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
   for (const Pass& p : plan.passes)
     STRIPE_CHECK(p.out_margin_px <= margin_pixels(p.cout), "margin contract too wide");
   for (Pass& p : plan.passes)
-    if (p.kind != PassKind::Pointwise && p.pro.has_post && p.pro.gray && p.pro.gmode == GrayMode::Ref) {
+    if (p.kind != PassKind::Pointwise && p.pro.has_post && p.pro.gray && p.pro.gmode == GrayMode::Ref &&
+        !p.pro.has_stat) {  // (a run-time table is never an affine map known here)
       p.post_aff = lut_affine(p.pro.post, &p.post_a, &p.post_b, &p.post_k);
       if (p.post_aff)
         p.desc += " post=clamp((" + std::to_string(p.post_a) + "v" + (p.post_b < 0 ? "" : "+") +
                   std::to_string(p.post_b) + ")>>" + std::to_string(p.post_k) + ")";
     }
   return plan;
+}
+
+Pass resolve_stat(const Pass& p, const Histogram& h) {
+  if (!p.pro.has_stat) return p;
+  STRIPE_CHECK(h.C == p.cin, "histogram has " << h.C << " channels, the pass reads " << p.cin);
+  Pass r = p;
+  const std::array<uint8_t, 256> t = stat_lut(p.pro.stat, h);
+  const bool pre = p.pro.gray || p.pro.cmat;
+  STRIPE_CHECK(pre ? p.pro.has_pre : p.pro.has_post, "statistic op without its table slot");
+  const std::array<uint8_t, 256>& after = pre ? p.pro.pre : p.pro.post;
+  std::array<uint8_t, 256>& out = pre ? r.pro.pre : r.pro.post;
+  for (int v = 0; v < 256; ++v) out[(size_t)v] = after[t[(size_t)v]];
+  r.pro.has_stat = false;
+  return r;
 }
 
 bool lut_affine(const std::array<uint8_t, 256>& lut, int* a_out, int* b_out, int* k_out) {

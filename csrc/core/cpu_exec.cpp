@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -378,6 +379,7 @@ void pointwise_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView o
 }  // namespace
 
 void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads) {
+  STRIPE_CHECK(!p.pro.has_stat, "statistic op not resolved (resolve_stat) before the pass runs");
   if (y1 <= y0) return;
   const int64_t row_bytes = (int64_t)W * p.cout;
   if (p.kind == PassKind::Conv) {  // float windows: the golden f64 sums themselves, row-parallel
@@ -397,12 +399,48 @@ void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0
                 [&](int ya, int yb) { stencil_rows(p, pt, in, out, W, g, ya, yb); });
 }
 
+Histogram cpu_histogram(ConstView in, int W, int C, int rows, int threads) {
+  STRIPE_CHECK(C == 1 || C == 3, "histogram needs 1 or 3 channels");
+  Histogram h(C);
+  std::mutex mu;
+  parallel_rows(0, rows, (int64_t)W * C, threads, [&](int ya, int yb) {
+    // a row block's private table (u32 per row: a row holds < 2^31 bytes)
+    std::vector<uint64_t> t((size_t)256 * C, 0);
+    uint32_t r[3][256];
+    for (int y = ya; y < yb; ++y) {
+      const uint8_t* s = in.origin + (int64_t)y * in.pitch;
+      std::memset(r, 0, sizeof r);
+      if (C == 1) {
+        for (int x = 0; x < W; ++x) ++r[0][s[x]];
+      } else {
+        for (int x = 0; x < W; ++x) {
+          ++r[0][s[3 * (size_t)x]];
+          ++r[1][s[3 * (size_t)x + 1]];
+          ++r[2][s[3 * (size_t)x + 2]];
+        }
+      }
+      for (int c = 0; c < C; ++c)
+        for (int v = 0; v < 256; ++v) t[(size_t)c * 256 + v] += r[c][v];
+    }
+    std::lock_guard<std::mutex> lk(mu);  // the blocks' tables summed at the end
+    for (size_t i = 0; i < t.size(); ++i) h.bins[i] += t[i];
+  });
+  return h;
+}
+
+Histogram cpu_histogram(const Image& img, int threads) {
+  return cpu_histogram(ConstView{img.data.data(), img.row_bytes()}, img.W, img.C, img.H, threads);
+}
+
 Image cpu_apply_plan(const Image& in, const Plan& plan, int threads) {
   STRIPE_CHECK(in.C == plan.cin, "image has " << in.C << " channels, chain expects " << plan.cin);
   if (plan.passes.empty()) return in;
   Image cur;  // the first pass reads the input in place (no copy of the frame)
   const Image* src = &in;
-  for (const Pass& p : plan.passes) {
+  for (const Pass& pp : plan.passes) {
+    // a statistic op: the table of this pass's input, the whole intermediate image
+    const Pass resolved = pp.data_dependent() ? resolve_stat(pp, cpu_histogram(*src, threads)) : Pass{};
+    const Pass& p = pp.data_dependent() ? resolved : pp;
     Image nxt(in.W, in.H, p.cout, NoInit{});  // cpu_pass writes every row of [0, H)
     cpu_pass(p, ConstView{src->data.data(), src->row_bytes()}, MutView{nxt.data.data(), nxt.row_bytes()}, in.W,
              RowGeom{0, in.H}, 0, in.H, threads);

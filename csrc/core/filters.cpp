@@ -303,10 +303,34 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
       STRIPE_CHECK(parts.size() > 1, "brightness needs a delta, e.g. brightness:40");
       op.ival = (int)parse_num(parts[1], tok);
       op.text = "brightness:" + std::to_string(op.ival);
+    } else if (name == "threshold" && parts.size() > 1 && trim(parts[1]) == "otsu") {
+      // Otsu's level of the global histogram, chosen at run time (filters.h)
+      STRIPE_CHECK(parts.size() == 2, "'" << tok << "': threshold:otsu takes no further arguments");
+      op.kind = OpKind::Stat;
+      op.stat = StatKind::Otsu;
+      op.text = "threshold:otsu";
     } else if (name == "threshold") {
       op.kind = OpKind::Threshold;
       op.ival = parts.size() > 1 ? (int)parse_num(parts[1], tok) : 128;
       op.text = "threshold:" + std::to_string(op.ival);
+    } else if (name == "equalize") {
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': equalize takes no arguments");
+      op.kind = OpKind::Stat;
+      op.stat = StatKind::Equalize;
+      op.text = "equalize";
+    } else if (name == "autocontrast") {
+      // autocontrast[:P]  P percent of the pixels clipped at each end, in hundredths
+      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': autocontrast syntax: autocontrast[:P]");
+      const double P = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 0.0;
+      STRIPE_CHECK(P >= 0.0 && P < 50.0, "'" << tok << "': autocontrast clips 0 <= P < 50 percent per end");
+      op.kind = OpKind::Stat;
+      op.stat = StatKind::AutoContrast;
+      op.ival = (int)std::nearbyint(100.0 * P);
+      STRIPE_CHECK(op.ival < 5000, "'" << tok << "': autocontrast clips 0 <= P < 50 percent per end");
+      std::ostringstream os;
+      os << "autocontrast";
+      if (op.ival != 0) os << ":" << op.ival / 100.0;
+      op.text = os.str();
     } else if (name == "expand" || name == "gray2rgb") {
       op.kind = OpKind::Expand;
       op.text = "expand";
@@ -423,8 +447,11 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
            "' (gray[:ref|bt601], contrast:F[:cv], invert, brightness:D, threshold:T, expand, "
            "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
            "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
-           "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv])");
+           "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv], "
+           "equalize, autocontrast[:P], threshold:otsu)");
     }
+    STRIPE_CHECK(op.kind != OpKind::Stat || !op.has_border,
+                 "'" << raw << "': " << op.text << " is a pointwise op and takes no @border");
     if (op.has_border) op.text += std::string("@") + border_name(op.border);
     ops.push_back(op);
   }
@@ -490,6 +517,100 @@ uint8_t gray_pixel(GrayMode m, uint8_t r, uint8_t g, uint8_t b) {
   }
   // OpenCV COLOR_BGR2GRAY, 8U: fixed point, yuv_shift 14, rounded (kern.cpp:73).
   return (uint8_t)((r * 4899 + g * 9617 + b * 1868 + (1 << 13)) >> 14);
+}
+
+// ---------------------------------------------------------------------------
+// Statistic ops (rules: filters.h)
+// ---------------------------------------------------------------------------
+namespace {
+// channels pooled: h[v] = sum_c hist[c][v]
+std::array<uint64_t, 256> pooled(const Histogram& hist) {
+  STRIPE_CHECK((hist.C == 1 || hist.C == 3) && hist.bins.size() == (size_t)256 * hist.C,
+               "histogram must hold 256 bins for 1 or 3 channels");
+  std::array<uint64_t, 256> h{};
+  for (int c = 0; c < hist.C; ++c)
+    for (int v = 0; v < 256; ++v) h[(size_t)v] += hist.at(c, v);
+  return h;
+}
+}  // namespace
+
+int otsu_level(const Histogram& hist) {
+  const std::array<uint64_t, 256> h = pooled(hist);
+  uint64_t N = 0, S = 0;
+  for (int v = 0; v < 256; ++v) {
+    N += h[(size_t)v];
+    S += (uint64_t)v * h[(size_t)v];
+  }
+  int best_t = 1;
+  double best = 0.0;
+  uint64_t n0 = 0, S0 = 0;
+  for (int t = 1; t < 256; ++t) {
+    n0 += h[(size_t)t - 1];
+    S0 += (uint64_t)(t - 1) * h[(size_t)t - 1];
+    const uint64_t n1 = N - n0;
+    double g = 0.0;
+    if (n0 != 0 && n1 != 0) {
+      // IEEE double, no contraction (the pragma above): every layer calls this one
+      const double p = (double)S0 * (double)N;
+      const double q = (double)n0 * (double)S;
+      const double a = p - q;
+      const double num = a * a;
+      const double den = (double)n0 * (double)n1;
+      g = num / den;
+    }
+    if (g > best) {  // strict: the smallest t attains the maximum
+      best = g;
+      best_t = t;
+    }
+  }
+  return best_t;
+}
+
+std::array<uint8_t, 256> stat_lut(const Op& op, const Histogram& hist) {
+  STRIPE_CHECK(op.kind == OpKind::Stat, "stat_lut: '" << op.text << "' is not a statistic op");
+  const std::array<uint64_t, 256> h = pooled(hist);
+  std::array<uint8_t, 256> lut{};
+  for (int v = 0; v < 256; ++v) lut[(size_t)v] = (uint8_t)v;
+  uint64_t cdf[256], N = 0;
+  for (int v = 0; v < 256; ++v) {
+    N += h[(size_t)v];
+    cdf[v] = N;
+  }
+  if (op.stat == StatKind::Otsu) {
+    const int T = otsu_level(hist);
+    for (int v = 0; v < 256; ++v) lut[(size_t)v] = v >= T ? 255 : 0;
+    return lut;
+  }
+  if (N == 0) return lut;  // no pixels: identity
+  if (op.stat == StatKind::Equalize) {
+    int v0 = 0;
+    while (h[(size_t)v0] == 0) ++v0;
+    const uint64_t c0 = h[(size_t)v0], D = N - c0;
+    if (D == 0) return lut;  // one grey level
+    for (int v = 0; v < 256; ++v) {
+      if (v < v0) {
+        lut[(size_t)v] = 0;
+        continue;
+      }
+      const uint64_t q = (510 * (cdf[v] - c0) + D) / (2 * D);
+      lut[(size_t)v] = (uint8_t)(q > 255 ? 255 : q);
+    }
+    return lut;
+  }
+  // autocontrast
+  const uint64_t cut = N * (uint64_t)op.ival / 10000;
+  int lo = 0;
+  while (lo < 255 && !(cdf[lo] > cut)) ++lo;
+  int hi = 255;
+  while (hi > 0 && !(N - cdf[hi - 1] > cut)) --hi;  // v = 0 always qualifies: cdf[-1] = 0, cut < N
+  if (hi <= lo) return lut;
+  const uint64_t d = (uint64_t)(hi - lo);
+  for (int v = 0; v < 256; ++v) {
+    if (v <= lo) lut[(size_t)v] = 0;
+    else if (v >= hi) lut[(size_t)v] = 255;
+    else lut[(size_t)v] = (uint8_t)((510 * (uint64_t)(v - lo) + d) / (2 * d));
+  }
+  return lut;
 }
 #pragma clang fp contract(on)
 

@@ -90,7 +90,19 @@ static int isqrt_round(int n) {
   return n > k * k + k ? k + 1 : k;
 }
 
+Histogram golden_histogram(const Image& img) {
+  STRIPE_CHECK(img.C == 1 || img.C == 3, "histogram needs 1 or 3 channels");
+  Histogram h(img.C);
+  for (int y = 0; y < img.H; ++y) {
+    const uint8_t* row = img.row(y);
+    for (int x = 0; x < img.W; ++x)
+      for (int c = 0; c < img.C; ++c) ++h.bins[(size_t)c * 256 + row[(size_t)x * img.C + c]];
+  }
+  return h;
+}
+
 void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1) {
+  STRIPE_CHECK(!p.pro.has_stat, "statistic op not resolved (resolve_stat) before the pass runs");
   if (y1 <= y0) return;
   if (p.kind == PassKind::Pointwise) {
     std::vector<uint8_t> o(3);
@@ -191,7 +203,9 @@ void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int
 Image golden_apply_plan(const Image& in, const Plan& plan) {
   STRIPE_CHECK(in.C == plan.cin, "image has " << in.C << " channels, chain expects " << plan.cin);
   Image cur = in;
-  for (const Pass& p : plan.passes) {
+  for (const Pass& pp : plan.passes) {
+    // a statistic op: the table of this pass's input, the whole intermediate image
+    const Pass p = pp.data_dependent() ? resolve_stat(pp, golden_histogram(cur)) : pp;
     Image nxt(in.W, in.H, p.cout);
     golden_pass(p, ConstView{cur.data.data(), cur.row_bytes()}, MutView{nxt.data.data(), nxt.row_bytes()},
                 in.W, RowGeom{0, in.H}, 0, in.H);

@@ -81,6 +81,25 @@ void launch_chunked(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
 
 }  // namespace
 
+void launch_histogram(const HistLaunch& L, hipStream_t s) {
+  // host-side shape checks before the kernel touches memory
+  STRIPE_CHECK(L.in && L.bins && L.W >= 1 && L.rows >= 0, "bad histogram launch");
+  STRIPE_CHECK(L.C == 1 || L.C == 3, "histogram needs 1 or 3 channels, got " << L.C);
+  STRIPE_CHECK((int64_t)L.W * L.C < (int64_t(1) << 31) - 16, "histogram: row of " << L.W << " pixels too wide");
+  STRIPE_CHECK(L.pitch >= align_up((int64_t)L.W * L.C, 16), "pitch too small for the histogram's rows");
+  // per-stripe bins are u32: a stripe holds fewer than 2^32 pixels
+  STRIPE_CHECK((int64_t)L.W * L.rows < (int64_t(1) << 32),
+               "histogram: a stripe of " << L.W << "x" << L.rows << " pixels overflows the u32 bins");
+  // the rows read (whole 16-byte groups) lie inside the allocation
+  STRIPE_CHECK(L.in_base && L.in >= L.in_base &&
+                   (L.rows == 0 || (L.in - L.in_base) + (int64_t)(L.rows - 1) * L.pitch +
+                                           align_up((int64_t)L.W * L.C, 16) <= L.in_bytes),
+               "histogram rows outside their buffer");
+  STRIPE_CHECK(((uintptr_t)L.in % 16 == 0) && L.pitch % 16 == 0, "histogram rows must be 16-byte aligned");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_hist_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

@@ -29,8 +29,16 @@ struct PointwiseProgram {
   bool has_post = false;
   std::array<uint8_t, 256> post{};
   bool expand = false;
+  // A statistic op (OpKind::Stat: equalize, autocontrast, threshold:otsu) as the
+  // program's FIRST stage.  Its table is built at run time from the histogram of
+  // the pass's input (resolve_stat) and composed in front of `pre` (programs
+  // with a gray or matrix stage; has_pre is set) or of `post` (otherwise;
+  // has_post is set).  The tables here hold the static ops after it, so the
+  // plan's structure never depends on table contents.
+  bool has_stat = false;
+  Op stat;
 
-  bool identity() const { return !has_pre && !gray && !cmat && !has_post && !expand; }
+  bool identity() const { return !has_pre && !gray && !cmat && !has_post && !expand && !has_stat; }
   bool lut_only() const { return !gray && !cmat && !expand && !has_pre; }
   // Prologue of a stencil pass may gray-convert and LUT, but not pre-LUT, expand
   // or mix channels (a colour matrix always runs as a pointwise pass of its own).
@@ -67,6 +75,8 @@ struct Pass {
   bool post_aff = false;
   int post_a = 1, post_b = 0, post_k = 0;
   std::string desc;
+  // the pass's LUT block is filled at run time from its input's histogram
+  bool data_dependent() const { return pro.has_stat; }
 };
 
 struct Plan {
@@ -78,11 +88,24 @@ struct Plan {
   Border in_margin_border = Border::Reflect101;
   std::vector<Pass> passes;
   std::string describe() const;
+  // some pass carries a statistic op: every schedule that assumes a static
+  // chain (deep halo, pipelined, graph replay, chunked transfers) declines
+  bool data_dependent() const {
+    for (const Pass& p : passes)
+      if (p.data_dependent()) return true;
+    return false;
+  }
 };
 
 // default_border: border for every stencil without an explicit @mode suffix.
 Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border,
                    bool fuse = true);
+
+// The pass with its statistic op resolved against `h`, the histogram of the
+// pass's input over the WHOLE frame (p.cin channels): stat_lut's table composed
+// in front of the static one, has_stat cleared.  A pass without one is returned
+// as it is.
+Pass resolve_stat(const Pass& p, const Histogram& h);
 
 // Gray-conversion parameters in the form the kernels use.
 // Find (a, b, k) with lut[v] == clamp((a * v + b) >> k, 0, 255) for every v

@@ -20,6 +20,12 @@ int cpu_threads(int ranks_per_host = 1);
 // Compute output rows [y0, y1) (local) of one compiled pass on `threads` threads.
 void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads);
 
+// Histogram of rows [0, rows) of a W x C view (bytes of a row beyond W * C are
+// never read): row blocks on up to `threads` threads, one private table per
+// thread, summed at the end.  Bit-identical to golden_histogram.
+Histogram cpu_histogram(ConstView in, int W, int C, int rows, int threads);
+Histogram cpu_histogram(const Image& img, int threads);
+
 // Whole-image helper (like golden_apply_plan).
 Image cpu_apply_plan(const Image& in, const Plan& plan, int threads);
 

@@ -218,6 +218,20 @@ class Engine {
   std::vector<int> caps() const;
   std::vector<int> policies() const;
   std::vector<int> orders() const;
+  // Histogram (256 x C u64 counts) of the engine's current image: the loaded
+  // input, or the last run()'s output.  Exactly this rank's own W x rows pixels
+  // are counted (device backend: k_hist on the compute stream; host backend:
+  // cpu_histogram); with a legacy partition that is the rows the partition keeps.
+  // global = false: this rank's rows only, no communication.
+  // global = true: the sum over all ranks, a collective every rank of the
+  // communicator calls: the active ranks send their counts to rank 0 in one
+  // group, rank 0 sums them (u64, on the host) and sends the total back in a
+  // second one (the broadcast_small pattern; host or device staging by the
+  // communicator's buffers; waits through Comm::wait, bounded by
+  // STRIPE_COMM_TIMEOUT_S).  A rank with 0 rows launches nothing and receives
+  // the total with the others (one more 6 KiB message from rank 0).  Synchronises
+  // the compute stream.
+  Histogram histogram(bool global = true);
   // Run the band / occupancy-cap autotune now (EngineConfig::autotune; otherwise
   // the first run() does it): keeps the tuning out of a timed region.
   void tune() {
@@ -339,6 +353,21 @@ class Engine {
   bool time_halo_ = true;  // record the halo stage events (last iteration of a run only)
   bool stage_timing_ = true;  // set_stage_timing
   void run_pass(const Pass& p, const uint8_t* in, uint8_t* out);
+  // Statistic passes (Pass::data_dependent).  Before such a pass runs, on the
+  // compute stream: the histogram of its input stripe, the all-reduce over the
+  // active ranks (every active rank runs every pass, so none waits for a rank
+  // that returned early), the table built and composed on the host
+  // (resolve_stat) and uploaded into the pass's LUT block.  One host
+  // synchronisation per such pass.  Returns the resolved pass (what the host
+  // backend executes).  The autotune launches such a pass with the LUT block
+  // as it stands (the static table: an identity statistic) and no collective.
+  Pass prepare_stat(const Pass& p, const uint8_t* in, int pi);
+  Histogram stripe_histogram(const uint8_t* org, int C);
+  Histogram reduce_histogram(const Histogram& local, bool idle_ranks_receive);
+  void fill_lut_block(const Pass& p, uint8_t* l) const;  // [pre | post | epi]
+  Buffer hist_dev_;          // device engine: the 256 x 3 u32 table k_hist adds to
+  Buffer hist_stage_;        // all-reduce staging where the communicator's buffers live
+  PinnedBuffer hist_host_;   // device engine: counts, LUT block and all-reduce staging on the host
   bool pipelined_ok() const;
   int chain_reach() const;  // sum of the chain's radii if every pass can extend its rows, else 0
   int choose_depth() const;

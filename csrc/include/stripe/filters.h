@@ -20,8 +20,33 @@
 //   out_c = sat_u8((sum_k q[c][k] * p_k + qb[c] + 2048) >> 12)   (>>: floor)
 // with q = nearbyint(m * 4096) and qb = nearbyint(b * 4096) (double, ties to
 // even), |q| <= 32767 (|m| < 8) and |b| <= 2048: every sum fits 27 bits.
+//
+// Statistic ops (equalize, autocontrast[:P], threshold:otsu): a per-byte table
+// computed from the GLOBAL histogram of the image as it enters the op (the
+// whole frame over all ranks, after every earlier op).  On RGB the three
+// channel histograms are pooled, h[v] = sum_c hist[c][v], and the one table is
+// applied to all three channels (no hue shift).  With N = sum h and
+// cdf[v] = sum_{u <= v} h[u], all in unsigned 64-bit integers (stat_lut):
+//   equalize      v0 = smallest v with h[v] > 0, c0 = h[v0], D = N - c0.
+//                 D == 0 (one grey level): identity.  Else lut[v] = 0 for
+//                 v < v0 and min(255, (510 (cdf[v] - c0) + D) / (2 D)) after:
+//                 OpenCV's equalizeHist rule, rounded exactly.
+//   autocontrast  P percent of the pixels clipped at each end, 0 <= P < 50,
+//                 Pq = nearbyint(100 P), cut = floor(N Pq / 10000).  lo =
+//                 smallest v with cdf[v] > cut, hi = largest v with
+//                 N - cdf[v-1] > cut (cdf[-1] = 0).  hi <= lo: identity.  Else
+//                 0 for v <= lo, 255 for v >= hi and
+//                 (510 (v - lo) + (hi - lo)) / (2 (hi - lo)) in between.
+//   threshold:otsu  p >= T ? 255 : 0 with T = otsu_level: for t = 1..255,
+//                 n0 = sum_{v<t} h, S0 = sum_{v<t} v h, n1 = N - n0,
+//                 S = sum v h; g(t) = 0 when n0 == 0 or n1 == 0, else
+//                 a a / ((double)n0 (double)n1), a = (double)S0 (double)N -
+//                 (double)n0 (double)S, in IEEE double without contraction;
+//                 T = the smallest t that attains the maximum (one grey
+//                 level: T = 1).
 #pragma once
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -39,6 +64,24 @@ enum class OpKind : int {
   Stencil,  // integer stencil with compile-time coefficients (stencil_defs.h)
   Conv,     // float KxK convolution (blur:K, conv:...), MFMA path on GPU
   ColorMatrix,  // 3 -> 3 channels: out_c = sat((sum_k q[c][k] p_k + qb[c] + 2048) >> 12)
+  Stat,     // per-byte table built at run time from the global histogram (Op::stat)
+};
+
+enum class StatKind : int { Equalize = 0, AutoContrast = 1, Otsu = 2 };
+
+// 256 counts per channel, [c * 256 + v]; C = 1 or 3 (0: empty).
+struct Histogram {
+  int C = 0;
+  std::vector<uint64_t> bins;
+
+  Histogram() = default;
+  explicit Histogram(int c) : C(c), bins((size_t)256 * c, 0) {}
+  uint64_t at(int c, int v) const { return bins[(size_t)c * 256 + v]; }
+  uint64_t total() const {
+    uint64_t n = 0;
+    for (uint64_t b : bins) n += b;
+    return n;
+  }
 };
 
 enum class GrayMode : int { BT601 = 0, Ref = 1 };
@@ -92,7 +135,8 @@ struct Op {
   GrayMode gray = GrayMode::BT601;
   RoundMode round = RoundMode::Trunc;
   float fval = 0.f;  // contrast factor
-  int ival = 0;      // brightness delta / threshold
+  int ival = 0;      // brightness delta / threshold / autocontrast Pq (hundredths of a percent)
+  StatKind stat = StatKind::Equalize;  // OpKind::Stat
   StencilId sid = StencilId::Gaussian5;
   int cm[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // colour matrix: q row-major, then qb (kColorShift)
   int K = 0;                  // conv window
@@ -122,6 +166,12 @@ inline uint8_t color_matrix_channel(const int* cm, int c, int r, int g, int b) {
                 kColorShift;  // arithmetic shift: floor
   return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
+
+// Statistic ops (rules at the top of this file): the table of `op`
+// (OpKind::Stat) for an image with histogram `h` (channels pooled), and Otsu's
+// level T in [1, 255].  The one definition every layer calls.
+std::array<uint8_t, 256> stat_lut(const Op& op, const Histogram& h);
+int otsu_level(const Histogram& h);
 
 // Gaussian weights exactly as specified for blur:K (OpenCV getGaussianKernel sigma rule).
 std::vector<double> gaussian_1d(int K, double sigma);

@@ -86,6 +86,23 @@ void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, 
 void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 void launch_conv(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 
+// Histogram of rows [0, rows) of a stripe (csrc/hip/histogram.hip k_hist): a
+// read-only pass that ADDS the counts of exactly the rows' W * C bytes (no
+// margin, halo row or pitch padding) to `bins`, 256 x C u32 on the device,
+// [c * 256 + v].  The caller zeroes `bins` on the same stream first.  A stripe
+// holds fewer than 2^32 pixels (checked), so a u32 bin cannot wrap.
+struct HistLaunch {
+  const uint8_t* in = nullptr;  // origin (local row 0, byte 0) of the stripe
+  int64_t pitch = 0;
+  int W = 0, C = 0, rows = 0;
+  const uint8_t* in_base = nullptr;  // the allocation `in` lies in (checked against the rows read)
+  int64_t in_bytes = 0;
+  uint32_t* bins = nullptr;
+};
+constexpr int kHistBins = 256 * 3;  // bins of the device table (RGB; gray uses the first 256)
+void launch_histogram(const HistLaunch& L, hipStream_t s);    // dispatch.cpp: checks, then the kernel
+void launch_hist_kernel(const HistLaunch& L, hipStream_t s);  // histogram.hip
+
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,
                          Border b, hipStream_t s);

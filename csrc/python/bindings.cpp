@@ -55,6 +55,36 @@ U8Array image_to_numpy(const Image& img) {
 
 hipStream_t as_stream(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Histograms cross as int64 arrays of shape (C, 256) (a (256,) array is one channel).
+using I64Array = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+
+py::array_t<int64_t> hist_to_numpy(const Histogram& h) {
+  py::array_t<int64_t> a(std::vector<py::ssize_t>{h.C, 256});
+  int64_t* d = a.mutable_data();
+  for (size_t i = 0; i < h.bins.size(); ++i) d[i] = (int64_t)h.bins[i];
+  return a;
+}
+
+Histogram hist_from_numpy(const I64Array& a) {
+  STRIPE_CHECK((a.ndim() == 1 && a.shape(0) == 256) || (a.ndim() == 2 && a.shape(1) == 256 &&
+                                                         (a.shape(0) == 1 || a.shape(0) == 3)),
+               "histogram must have shape (256,), (1, 256) or (3, 256)");
+  Histogram h(a.ndim() == 1 ? 1 : (int)a.shape(0));
+  const int64_t* s = a.data();
+  for (size_t i = 0; i < h.bins.size(); ++i) {
+    STRIPE_CHECK(s[i] >= 0, "histogram counts must not be negative");
+    h.bins[i] = (uint64_t)s[i];
+  }
+  return h;
+}
+
+Op stat_op(const std::string& token) {
+  auto ops = parse_chain(token);
+  STRIPE_CHECK(ops.size() == 1 && ops[0].kind == OpKind::Stat,
+               "'" << token << "' is not one statistic op (equalize, autocontrast[:P], threshold:otsu)");
+  return ops[0];
+}
+
 // Comm wrapper owning its hub reference (Python-visible handle).
 struct PyComm {
   std::unique_ptr<Comm> comm;
@@ -223,9 +253,11 @@ PYBIND11_MODULE(_C, m) {
       q["epi_expand"] = ps.epi_expand;
       q["out_margin_px"] = ps.out_margin_px;
       q["cmat"] = ps.pro.cmat;
+      q["stat"] = ps.pro.has_stat ? ps.pro.stat.text : std::string();  // statistic op leading the program
       passes.append(q);
     }
     d["passes"] = passes;
+    d["data_dependent"] = p.data_dependent();
     return d;
   }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true);
 
@@ -300,6 +332,25 @@ PYBIND11_MODULE(_C, m) {
     }
     return image_to_numpy(out);
   }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101");
+
+  // ---- histogram and the statistic ops' tables ----
+  m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
+        py::arg("image"), "int64 counts of shape (C, 256)");
+  m.def("cpu_histogram", [](const U8Array& a, int threads) {
+    Image img = image_from_numpy(a);
+    Histogram h;
+    {
+      py::gil_scoped_release nogil;
+      h = cpu_histogram(img, threads > 0 ? threads : cpu_threads());
+    }
+    return hist_to_numpy(h);
+  }, py::arg("image"), py::arg("threads") = 0, "golden_histogram on the host executor's threads");
+  m.def("stat_lut", [](const std::string& token, const I64Array& hist) {
+    const std::array<uint8_t, 256> l = stat_lut(stat_op(token), hist_from_numpy(hist));
+    return std::vector<int>(l.begin(), l.end());
+  }, py::arg("token"), py::arg("hist"),
+        "the 256-entry table of equalize | autocontrast[:P] | threshold:otsu for a (C, 256) histogram (channels pooled)");
+  m.def("otsu_level", [](const I64Array& hist) { return otsu_level(hist_from_numpy(hist)); }, py::arg("hist"));
 
   // ---- partition ----
   m.def("plan_rows", [](int H, int world, int min_rows, bool legacy) {
@@ -586,6 +637,20 @@ PYBIND11_MODULE(_C, m) {
     c->comm = make_staged_comm(std::move(host->comm), device);
     return c;
   });
+  // `world` in-process ranks over one hub (device = true: device buffers on the
+  // current GPU, the `local` backend; false: host buffers).  The caller drives
+  // one engine per communicator, one thread each (the engine calls release the GIL).
+  m.def("make_local_comms", [](int world, bool device, double timeout_s) {
+    STRIPE_CHECK(world >= 1, "make_local_comms needs world >= 1");
+    auto hub = make_local_hub(world, device, timeout_s);
+    py::list v;
+    for (int r = 0; r < world; ++r) {
+      auto c = std::make_unique<PyComm>();
+      c->comm = make_local_comm(hub, r);
+      v.append(py::cast(std::move(c)));
+    }
+    return v;
+  }, py::arg("world"), py::arg("device"), py::arg("timeout_s") = 60.0);
 
   // ---- engine ----
   py::class_<EngineConfig>(m, "EngineConfig")
@@ -707,6 +772,16 @@ PYBIND11_MODULE(_C, m) {
         e.run(it);
       }, py::arg("iterations") = 1)
       .def("rewind", &Engine::rewind)
+      .def("histogram", [](Engine& e, bool global) {
+        Histogram h;
+        {
+          py::gil_scoped_release nogil;
+          h = e.histogram(global);
+        }
+        return hist_to_numpy(h);
+      }, py::arg("global_") = true,
+           "int64 counts (C, 256) of the current image: this rank's rows (global_=False) or the sum over all "
+           "ranks (a collective every rank calls)")
       .def("alloc_host_io", &Engine::alloc_host_io)
       .def("host_input", [](py::object self) {
         Engine& e = self.cast<Engine&>();

@@ -145,12 +145,10 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   prt_.resize(plan_.passes.size());
   for (size_t i = 0; i < plan_.passes.size(); ++i) {
     const Pass& p = plan_.passes[i];
+    // (a statistic pass: the static tables, i.e. an identity statistic, until
+    // prepare_stat uploads the table of the pass's input)
     std::vector<uint8_t> l(kLutBytes);
-    for (int v = 0; v < 256; ++v) {
-      l[v] = p.pro.has_pre ? p.pro.pre[v] : (uint8_t)v;
-      l[256 + v] = p.pro.has_post ? p.pro.post[v] : (uint8_t)v;
-      l[512 + v] = p.has_epi ? p.epi[v] : (uint8_t)v;
-    }
+    fill_lut_block(p, l.data());
     prt_[i].luts = Buffer(kLutBytes, device());
     if (device()) {
       HIP_CHECK(hipMemcpy(prt_[i].luts.data(), l.data(), kLutBytes, hipMemcpyHostToDevice));
@@ -582,7 +580,7 @@ void Engine::post_halo_ops(uint8_t* org, int C, int R, hipStream_t s) {
 
 bool Engine::posts_halo() const {
   return device() && comm_ && cfg_.halo && neighbours() && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
-         plan_.passes[0].R > 0 && stripe().rows > 0;
+         plan_.passes[0].R > 0 && stripe().rows > 0 && !plan_.data_dependent();
 }
 
 void Engine::post_halo() {
@@ -685,6 +683,10 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
   const Stripe& st = stripe();
   const int rows = st.rows;
   if (rows == 0) return;
+  // a statistic op: the table of this pass's input over all active ranks, in
+  // the pass's LUT block (device) / in the resolved pass (host)
+  Pass resolved;
+  if (p.data_dependent()) resolved = prepare_stat(p, in, (int)(&p - plan_.passes.data()));
   const RowGeom g = geom();
   const int R = p.R;
   const bool xchg = !halo_done_ && ((cfg_.halo && R > 0 && neighbours()) || (device() && schedule_emu() == 1 && R > 0));
@@ -710,7 +712,8 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
   }
   if (!device()) {
     if (xchg) exchange_halo(const_cast<uint8_t*>(in), p.cin, R, nullptr);
-    cpu_pass(p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, g, 0, rows, host_threads());
+    cpu_pass(p.data_dependent() ? resolved : p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, g, 0,
+             rows, host_threads());
     return;
   }
   const size_t pi = (size_t)(&p - plan_.passes.data());
@@ -764,6 +767,7 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
 // chain without halo exchange.  (RCCL calls are kept out of captured graphs.)
 bool Engine::graph_ok() const {
   if (!device() || !cfg_.graphs) return false;
+  if (plan_.data_dependent()) return false;  // a statistic pass synchronises and may reduce over the ranks
   const bool comm = cfg_.halo && plan_.max_radius > 0 && neighbours();
   return !comm && stripe().rows > 0;
 }

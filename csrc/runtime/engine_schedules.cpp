@@ -35,6 +35,7 @@ namespace stripe {
 // core/rim events alternate by step parity so core_k never waits rim_k.
 // ---------------------------------------------------------------------------
 bool Engine::pipelined_ok() const {
+  if (plan_.data_dependent()) return false;  // statistic passes take the plain per-pass path
   if (device() && schedule_emu() == 2 && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
       stripe().rows > 4 * plan_.passes[0].R && plan_.passes[0].R > 0)
     return true;
@@ -140,6 +141,9 @@ void Engine::run_pipelined(int iterations) {
 // passes (32-row group grid) keep the per-pass exchange.
 // ---------------------------------------------------------------------------
 int Engine::chain_reach() const {
+  // a statistic pass needs the histogram of its whole input before it runs: no
+  // deep halo, no deep steps (the recomputed neighbour rows would need it too)
+  if (plan_.data_dependent()) return 0;
   int s = 0;
   for (const Pass& p : plan_.passes) {
     if (p.kind != PassKind::Pointwise && p.kind != PassKind::Separable && p.kind != PassKind::Direct) return 0;

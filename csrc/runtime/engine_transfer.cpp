@@ -124,7 +124,8 @@ void Engine::run_e2e(int chunks) {
     HIP_CHECK(hipEventRecord(ev_h2d_[i], s_h2d_));
   }
   stage_end(Stage::H2D, s_h2d_);
-  const bool single = plan_.passes.size() == 1;
+  // (a statistic pass needs its whole input before it runs: unpipelined too)
+  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent();
   if (!single) {
     // multi-pass chains: upload overlapped with nothing but the download of the
     // previous step; the chain itself runs as usual
@@ -231,6 +232,7 @@ void Engine::join_d2h() {
 // ---------------------------------------------------------------------------
 int Engine::dist_chunks(int chunks) const {
   if (!comm_ || part_.active <= 1 || chunks < 2 || plan_.passes.size() != 1) return 0;
+  if (plan_.data_dependent()) return 0;  // the table needs the whole frame: scatter, run, gather
   const Pass& p = plan_.passes[0];
   if (p.kind != PassKind::Separable && p.kind != PassKind::Direct && p.kind != PassKind::Pointwise) return 0;
   if (cfg_.halo && p.R > halo_) return 0;
@@ -243,6 +245,7 @@ int Engine::dist_chunks(int chunks) const {
 bool Engine::dist_direct() const {
   if (!device() || part_.active != 1 || rank_ != 0 || plan_.passes.size() != 1) return false;
   if (!root_in_.data() || !root_out_.data()) return false;
+  if (plan_.data_dependent()) return false;  // prepare_stat reads the stripe buffers
   const Pass& p = plan_.passes[0];
   return p.kind == PassKind::Separable || p.kind == PassKind::Direct || p.kind == PassKind::Pointwise;
 }
@@ -469,7 +472,8 @@ void Engine::run_to_host(void* dst, int chunks) {
   HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_[2], 0));
   stage_begin(Stage::E2E, s_compute_);
   const Pass& p0 = plan_.passes[0];
-  const bool single = plan_.passes.size() == 1;  // any kind: launch_pass takes row ranges
+  // any kind: launch_pass takes row ranges (a statistic pass goes through run())
+  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent();
   if (!single) {  // multi-pass chains: the chain, then the download
     run(1);
     const int ob = out_buf_;

@@ -128,6 +128,10 @@ void Engine::autotune_bands() {
   for (size_t i = 0; i < plan_.passes.size(); ++i) {
     const Pass& p = plan_.passes[i];
     if (p.kind != PassKind::Separable && p.kind != PassKind::Direct) continue;
+    // (a pass with a statistic op in its prologue is timed with the LUT block as
+    // it stands -- the static table, an identity statistic -- and without its
+    // histogram or all-reduce: the candidate loops differ per rank unless the
+    // tune is reduced, so a collective inside them would deadlock)
     PassLaunch L = make_launch(p, origin(buf_[cur_], p.cin), origin(buf_[cur_ ^ 1], p.cout), (int)i);
     L.ry[0] = 0;
     L.ry[1] = L.rows;

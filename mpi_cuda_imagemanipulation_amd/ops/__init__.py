@@ -41,6 +41,18 @@ FILTERS = {
     "saturation:S (saturate:S)": "mix with the BT.601 luma: 0 = gray, 1 = identity, > 1 = more colour; gray pixels stay",
     "swaprb (bgr)": "swap the R and B channels (RGB <-> BGR)",
     "ycbcr / ycbcr:inv": "JFIF full-range RGB -> (Y, Cb, Cr) and back",
+    # statistic ops: one per-byte table from the GLOBAL histogram of the image as it enters the op (the whole
+    # frame over all ranks); on RGB the three channel histograms are pooled, h[v] = sum_c hist[c][v], and the
+    # one table is applied to all channels (no hue shift).  N = sum h, cdf[v] = sum_{u<=v} h[u], u64 integers.
+    # Each costs one read-only histogram pass (k_hist), one small all-reduce and one host synchronisation.
+    "equalize": "histogram equalisation (OpenCV equalizeHist, exact): v0 = first v with h[v] > 0, c0 = h[v0], "
+                "D = N - c0; D == 0: identity; else 0 for v < v0 and min(255, (510 (cdf[v] - c0) + D) / (2 D))",
+    "autocontrast[:P]": "contrast stretch clipping P percent (0 <= P < 50, default 0) of the pixels per end: "
+                        "Pq = nearbyint(100 P), cut = N Pq / 10000; lo = first v with cdf[v] > cut, hi = last v "
+                        "with N - cdf[v-1] > cut; hi <= lo: identity; else 0 for v <= lo, 255 for v >= hi, "
+                        "(510 (v - lo) + (hi - lo)) / (2 (hi - lo)) between",
+    "threshold:otsu": "p >= T ? 255 : 0 with Otsu's T: the smallest t in 1..255 maximising "
+                      "(S0 N - n0 S)^2 / (n0 n1) in double (n0, S0: count and sum below t; one grey level: T = 1)",
     # stencils
     "emboss3 / emboss5": "kernel.cu:64-94 filters (3x3 and diagonal 5x5)",
     "gaussian3/5/7": "binomial Gaussian, integer, rounded",
@@ -282,6 +294,61 @@ def large_blur(x, ksize: int = 31, sigma: float = 0.0, border: str = "reflect101
     return apply(x, f"blur:{ksize}:{sigma}" if sigma > 0 else f"blur:{ksize}", border)
 
 
+# ---- histogram and the statistic ops ---------------------------------------------
+def histogram(image):
+    """Per-channel histogram: an int64 numpy array of shape (C, 256) (C = 1 or 3) counting exactly the
+    image's H x W pixels.  A CUDA tensor is counted by the k_hist HIP kernel on torch's current stream
+    (through the cached engine, like `apply`); a numpy array / CPU tensor by the threaded host executor.
+    A BxHxWxC batch gives (B, C, 256)."""
+    if image.ndim == 4:
+        if image.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(image.shape)}")
+        hs = [histogram(image[b]) for b in range(image.shape[0])]
+        return np.stack(hs) if hs else np.empty((0, image.shape[3], 256), np.int64)
+    if _is_tensor(image) and image.is_cuda:
+        if image.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        x = image.contiguous()
+        W, H, Cc = _shape(x)
+        # any chain does: the engine only holds the padded stripe the kernel reads
+        eng = _engine(W, H, Cc, "invert", "reflect101", True, x.device.index)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        with eng._lock:
+            if eng._stream != stream:
+                eng.use_external_stream(stream)
+                eng._stream = stream
+            eng.load_packed_ptr(x.data_ptr(), True)
+            h = eng.histogram(False)  # synchronises the stream: x has been consumed
+        return h
+    arr = image.numpy() if _is_tensor(image) else np.asarray(image)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    if arr.ndim == 3 and arr.shape[2] == 1:
+        arr = arr[:, :, 0]
+    _shape(arr)
+    return C.cpu_histogram(np.ascontiguousarray(arr))
+
+
+def equalize(x):
+    """Histogram equalisation (one table from the pooled channels, `FILTERS['equalize']`)."""
+    return apply(x, "equalize")
+
+
+def autocontrast(x, cutoff: float = 0.0):
+    """Contrast stretch clipping `cutoff` percent of the pixels at each end (0 <= cutoff < 50)."""
+    return apply(x, f"autocontrast:{float(cutoff)!r}")
+
+
+def threshold_otsu(x):
+    """Binarise at Otsu's level of the image's own histogram."""
+    return apply(x, "threshold:otsu")
+
+
+def otsu_level(x) -> int:
+    """Otsu's level T in [1, 255] of the image (channels pooled): threshold_otsu(x) == (x >= T) * 255."""
+    return int(C.otsu_level(histogram(x)))
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -292,4 +359,5 @@ __all__ = [
     "gaussian_blur", "box_blur", "sobel", "sharpen", "laplace", "emboss",
     "median", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
     "color_matrix", "sepia", "saturation", "swap_rb", "rgb_to_ycbcr", "ycbcr_to_rgb",
+    "histogram", "equalize", "autocontrast", "threshold_otsu", "otsu_level",
 ]

@@ -58,6 +58,7 @@ CORE_SOURCES = [
     "hip/conv.hip",
     "hip/blur_sep.hip",
     "hip/jpeg_dev.hip",
+    "hip/histogram.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
@@ -66,6 +67,7 @@ CORE_SOURCES = [
     "runtime/engine_tune.cpp",
     "runtime/engine_transfer.cpp",
     "runtime/engine_group.cpp",
+    "runtime/engine_stats.cpp",
     "runtime/trace.cpp",
 ]
 # plain host C++ (no device compilation): CPU multiversioning (target_clones)
