@@ -309,6 +309,33 @@ int cmd_run(const Args& a) {
     std::cerr << compile_chain(parse_chain(cfg.chain), cfg.C, cfg.border, cfg.fuse).describe();
     std::cerr << plan_rows(cfg.H, N, 1, cfg.legacy_partition).describe() << "\n";
   }
+  if (a.has("held")) {
+    // --held FILE: a second image of equal size as the external held image (the
+    // two-image form of the combine ops): one engine, no scatter / gather
+    STRIPE_CHECK(N == 1, "--held is single-process only (--ranks 1), got --ranks " << N);
+    const Image held = read_image(a.get("held"));
+    const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
+    STRIPE_CHECK(held.W == cur.W && held.H == cur.H && held.C == cur.C,
+                 "--held image is " << held.W << "x" << held.H << "x" << held.C << ", the input " << cur.W << "x"
+                                    << cur.H << "x" << cur.C);
+    cfg.held_input = true;
+    const std::vector<int> devs = parse_int_list(a.get("devices"));
+    if (cfg.backend == BackendKind::Device) cfg.device = devs.empty() ? 0 : devs[0];
+    const auto t0 = std::chrono::steady_clock::now();
+    Engine e(cfg, nullptr);
+    e.load_packed(cur.data.data(), false);
+    e.load_held_packed(held.data.data(), false);
+    e.run(iters);
+    Image out(cfg.W, cfg.H, e.out_channels(), NoInit{});
+    e.store_packed(out.data.data(), false);
+    e.synchronize();
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    write_image(a.get("output"), out, a.geti("quality", 95));
+    std::printf("{\"cmd\":\"run\",\"W\":%d,\"H\":%d,\"C\":%d,\"ranks\":1,\"backend\":\"%s\",\"chain\":\"%s\","
+                "\"held\":true,\"wall_ms\":%.3f,\"kernel_ms\":%.4f}\n",
+                in.W, in.H, in.C, backend.c_str(), cfg.chain.c_str(), ms, e.times().run);
+    return 0;
+  }
   Group g = make_group(backend, N, parse_int_list(a.get("devices")));
   PhaseTimes t;
   const auto t0 = std::chrono::steady_clock::now();
@@ -687,6 +714,7 @@ void usage() {
                "        [--backend rccl|local|host] [--devices 0,1,..] [--border MODE] [--no-halo]\n"
                "        [--expand-gray] [--legacy-partition] [--iterations K] [--no-fuse] [--no-overlap]\n"
                "        [--dist-chunks K]  (> 1 ranks, single-pass chains: pipelined scatter/filter/gather)\n"
+               "        [--held other.ppm]  (a second image of equal size, held for add/sub/absdiff/blend:t/...; --ranks 1)\n"
                "        one process per rank: --backend rccl --world N --rank r --rendezvous FILE [--device d]\n"
                "  bench --synthetic WxHxC [--seed S] [--chain C] [--ranks 1,2,4,8] [--iters N] [--warmup N]\n"
                "        [--scope resident|device,dist,e2e] [--backend rccl|local|host] [--json out.json]\n"

@@ -126,14 +126,31 @@ std::string Plan::describe() const {
   return os.str();
 }
 
-Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, bool fuse) {
+Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, bool fuse, int held_c) {
   STRIPE_CHECK(cin == 1 || cin == 3, "input must have 1 or 3 channels, got " << cin);
+  STRIPE_CHECK(held_c == 0 || held_c == cin, "the held image has " << held_c << " channels, the input " << cin);
   Plan plan;
   plan.spec = chain_to_string(ops);
   plan.cin = cin;
+  plan.held_c = held_c;
   int c = cin;
   PointwiseProgram pending;
   int pending_cin = c;
+  // the held slot: its channel count (0: empty), the slot actions since the
+  // last pass (they go with the next pass), and whether the image the last
+  // `hold` kept has been read by a combine or a swap
+  int hc = held_c;
+  std::string pending_slots;
+  bool hold_unread = false;
+  auto take_slots = [&](Pass& p) {
+    p.slots = pending_slots;
+    pending_slots.clear();
+    if (!p.slots.empty()) {
+      std::string names;
+      for (char a : p.slots) names += std::string(names.empty() ? "" : ",") + (a == 'h' ? "hold" : "swap");
+      p.desc = "[" + names + "] " + p.desc;
+    }
+  };
 
   auto flush_pointwise = [&]() {
     normalize(pending);
@@ -146,6 +163,7 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
       p.pro = pending;
       p.desc = "pointwise[" + prog_desc(pending) + "] " + std::to_string(p.cin) + "->" +
                std::to_string(p.cout) + "ch";
+      take_slots(p);
       plan.passes.push_back(p);
     }
     pending = PointwiseProgram{};
@@ -162,7 +180,19 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     normalize(pending);
     if (pending.identity()) return;
     Pass* last = plan.passes.empty() ? nullptr : &plan.passes.back();
-    const bool epi_ok = fuse && last && !pending.has_stat &&
+    // (a slot action since the last pass: the run works on another image than
+    // that pass wrote, so it is a pass of its own)
+    if (fuse && last && pending_slots.empty() && last->kind == PassKind::Combine && !last->pro.has_post &&
+        !pending.has_stat && pending.lut_only() && pending.has_post) {
+      // a LUT-only run after a combine op: that pass's post table
+      last->pro.has_post = true;
+      last->pro.post = pending.post;
+      last->desc += " post[lut]";
+      pending = PointwiseProgram{};
+      pending_cin = c;
+      return;
+    }
+    const bool epi_ok = fuse && last && !pending.has_stat && pending_slots.empty() &&
                         (last->kind == PassKind::Separable || last->kind == PassKind::Direct) &&
                         !last->has_epi && !last->epi_expand && !pending.gray && !pending.cmat && !pending.has_pre &&
                         (!pending.expand || last->cmid == 1);
@@ -183,7 +213,46 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
     }
   };
 
+  STRIPE_CHECK(ops.empty() || ops.back().kind != OpKind::Swap,
+               "'swap' is the chain's last op: the image it makes current is the chain's result unchanged");
   for (const Op& op : ops) {
+    if (op.slot()) {
+      // the image a slot op names must exist in a buffer: the pending run is flushed
+      flush_tail();
+      if (op.kind == OpKind::Hold) {
+        STRIPE_CHECK(!hold_unread, "'hold': the image held before is replaced without any op having read it");
+        hc = c;
+        hold_unread = true;
+        pending_slots += 'h';
+      } else {
+        STRIPE_CHECK(hc != 0, "'swap': nothing is held (hold first)");
+        std::swap(c, hc);
+        pending_cin = c;
+        hold_unread = false;
+        pending_slots += 's';
+      }
+      continue;
+    }
+    if (op.kind == OpKind::Combine) {
+      STRIPE_CHECK(hc != 0, "'" << op.text << "': nothing is held (hold first)");
+      STRIPE_CHECK(hc == c, "'" << op.text << "': the current image has " << c << " channel(s), the held image "
+                                << hc);
+      // the pending run: the previous stencil's epilogue or a pass of its own (never part of this pass)
+      flush_tail();
+      Pass p;
+      p.kind = PassKind::Combine;
+      p.cin = p.cmid = p.cout = c;
+      p.comb = op.comb;
+      std::copy(op.cq, op.cq + 3, p.cq);
+      p.cd = op.ival;
+      p.desc = "combine " + op.text + " " + std::to_string(c) + "ch";
+      take_slots(p);
+      plan.passes.push_back(p);
+      hold_unread = false;
+      pending = PointwiseProgram{};
+      pending_cin = c;
+      continue;
+    }
     if (op.pointwise()) {
       switch (op.kind) {
         case OpKind::Stat:
@@ -267,11 +336,24 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
                (pro.empty() ? "" : " prologue[" + pro + "]") + " " + std::to_string(p.cin) +
                "->" + std::to_string(p.cout) + "ch border=" + border_name(p.border);
     }
+    take_slots(p);
     plan.passes.push_back(p);
     pending = PointwiseProgram{};
     pending_cin = c;
   }
   flush_tail();  // trailing pointwise ops
+  STRIPE_CHECK(!hold_unread, "'hold': no later op reads the held image");
+  if (!pending_slots.empty()) {
+    // slot actions with no pass behind them (the run after them normalised to
+    // the identity, e.g. `...,swap,invert,invert`): a copy pass carries them,
+    // so the image they make current is the chain's result in every layer
+    Pass p;
+    p.kind = PassKind::Pointwise;
+    p.cin = p.cout = p.cmid = c;
+    p.desc = "pointwise[copy]";
+    take_slots(p);
+    plan.passes.push_back(p);
+  }
   if (plan.passes.empty()) {  // identity chain: keep one copy pass so outputs are fresh
     Pass p;
     p.kind = PassKind::Pointwise;
@@ -295,6 +377,16 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
   }
   plan.in_margin_px = next_r;
   plan.in_margin_border = next_b;
+  if (plan.branched()) {
+    // no producer maintains margins (Pass::fill_in): every stencil fills its own input's
+    for (Pass& p : plan.passes) {
+      p.out_margin_px = 0;
+      p.out_margin_border = Border::Reflect101;
+      p.fill_in = p.R > 0 && p.kind != PassKind::Pointwise && p.kind != PassKind::Combine;
+    }
+    plan.in_margin_px = 0;
+    plan.in_margin_border = Border::Reflect101;
+  }
   // a chain that maps C -> C can be iterated (ping-pong): the last pass then
   // feeds the first one, so it must maintain the first pass's input margins.
   // A pointwise pass maps its input margins byte by byte, so the contract

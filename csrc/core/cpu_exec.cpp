@@ -362,6 +362,57 @@ void stencil_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out
   }
 }
 
+// Combine pass: a row-wide byte sweep per op, combine_rule's arithmetic term for term.
+STRIPE_SIMD void combine_sweep(CombineKind k, const int* cq, int d, const uint8_t* __restrict x,
+                               const uint8_t* __restrict h, uint8_t* __restrict o, int64_t n) {
+  switch (k) {
+    case CombineKind::Add:
+      for (int64_t i = 0; i < n; ++i) {
+        const int v = x[i] + h[i];
+        o[i] = (uint8_t)(v > 255 ? 255 : v);
+      }
+      break;
+    case CombineKind::Sub:
+      for (int64_t i = 0; i < n; ++i) o[i] = (uint8_t)(h[i] > x[i] ? h[i] - x[i] : 0);
+      break;
+    case CombineKind::RSub:
+      for (int64_t i = 0; i < n; ++i) o[i] = (uint8_t)(x[i] > h[i] ? x[i] - h[i] : 0);
+      break;
+    case CombineKind::AbsDiff:
+      for (int64_t i = 0; i < n; ++i) o[i] = (uint8_t)(x[i] > h[i] ? x[i] - h[i] : h[i] - x[i]);
+      break;
+    case CombineKind::Min:
+      for (int64_t i = 0; i < n; ++i) o[i] = x[i] < h[i] ? x[i] : h[i];
+      break;
+    case CombineKind::Max:
+      for (int64_t i = 0; i < n; ++i) o[i] = x[i] > h[i] ? x[i] : h[i];
+      break;
+    case CombineKind::LinComb: {
+      const int32_t qa = cq[0], qb = cq[1], q0 = cq[2] + (1 << (kColorShift - 1));
+      for (int64_t i = 0; i < n; ++i) {
+        const int32_t v = (qa * (int32_t)x[i] + qb * (int32_t)h[i] + q0) >> kColorShift;
+        o[i] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+      }
+      break;
+    }
+    case CombineKind::Above:
+      for (int64_t i = 0; i < n; ++i) o[i] = (int)h[i] - (int)x[i] + d > 0 ? 255 : 0;
+      break;
+    default:
+      break;
+  }
+}
+
+void combine_rows(const Pass& p, ConstView in, ConstView in2, MutView out, int W, int ya, int yb) {
+  const int64_t E = (int64_t)W * p.cin;
+  for (int y = ya; y < yb; ++y) {
+    uint8_t* dst = out.origin + (int64_t)y * out.pitch;
+    combine_sweep(p.comb, p.cq, p.cd, in.origin + (int64_t)y * in.pitch, in2.origin + (int64_t)y * in2.pitch, dst, E);
+    if (p.pro.has_post)
+      for (int64_t i = 0; i < E; ++i) dst[i] = p.pro.post[dst[i]];
+  }
+}
+
 void pointwise_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out, int W, int ya, int yb) {
   std::vector<uint8_t> tmp(p.pro.expand ? (size_t)W * pt.cmid : 0);
   for (int y = ya; y < yb; ++y) {
@@ -378,10 +429,16 @@ void pointwise_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView o
 
 }  // namespace
 
-void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads) {
+void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads,
+              ConstView in2) {
   STRIPE_CHECK(!p.pro.has_stat, "statistic op not resolved (resolve_stat) before the pass runs");
   if (y1 <= y0) return;
   const int64_t row_bytes = (int64_t)W * p.cout;
+  if (p.kind == PassKind::Combine) {
+    STRIPE_CHECK(in2.origin != nullptr, "combine pass without a held image");
+    parallel_rows(y0, y1, row_bytes, threads, [&](int ya, int yb) { combine_rows(p, in, in2, out, W, ya, yb); });
+    return;
+  }
   if (p.kind == PassKind::Conv) {  // float windows: the golden f64 sums themselves, row-parallel
     parallel_rows(y0, y1, row_bytes * p.K * p.K, threads,
                   [&](int ya, int yb) { golden_pass(p, in, out, W, g, ya, yb); });
@@ -432,9 +489,32 @@ Histogram cpu_histogram(const Image& img, int threads) {
   return cpu_histogram(ConstView{img.data.data(), img.row_bytes()}, img.W, img.C, img.H, threads);
 }
 
-Image cpu_apply_plan(const Image& in, const Plan& plan, int threads) {
+Image cpu_apply_plan(const Image& in, const Plan& plan, int threads, const Image* held_in) {
   STRIPE_CHECK(in.C == plan.cin, "image has " << in.C << " channels, chain expects " << plan.cin);
+  STRIPE_CHECK((plan.held_c != 0) == (held_in != nullptr), "the chain was compiled " << (plan.held_c ? "for" : "without")
+                                                               << " an external held image");
+  STRIPE_CHECK(!held_in || (held_in->W == in.W && held_in->H == in.H && held_in->C == plan.held_c),
+               "the held image must have the input's size and " << plan.held_c << " channel(s)");
   if (plan.passes.empty()) return in;
+  if (plan.branched()) {
+    // current and held images are shared, never copied: hold and swap move pointers
+    std::shared_ptr<const Image> cur(&in, [](const Image*) {}), held;
+    if (held_in) held = std::shared_ptr<const Image>(held_in, [](const Image*) {});
+    for (const Pass& pp : plan.passes) {
+      for (char a : pp.slots) {
+        if (a == 'h') held = cur;
+        else std::swap(cur, held);
+      }
+      const Pass resolved = pp.data_dependent() ? resolve_stat(pp, cpu_histogram(*cur, threads)) : Pass{};
+      const Pass& p = pp.data_dependent() ? resolved : pp;
+      auto nxt = std::make_shared<Image>(in.W, in.H, p.cout, NoInit{});
+      const ConstView hv = held ? ConstView{held->data.data(), held->row_bytes()} : ConstView{};
+      cpu_pass(p, ConstView{cur->data.data(), cur->row_bytes()}, MutView{nxt->data.data(), nxt->row_bytes()}, in.W,
+               RowGeom{0, in.H}, 0, in.H, threads, hv);
+      cur = nxt;
+    }
+    return *cur;
+  }
   Image cur;  // the first pass reads the input in place (no copy of the frame)
   const Image* src = &in;
   for (const Pass& pp : plan.passes) {

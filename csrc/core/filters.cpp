@@ -134,7 +134,21 @@ void set_color_matrix(Op& op, const double (&m)[9], const double (&b)[3], const 
   }
 }
 
+// A Q12 coefficient as the decimal that parses back to it (q / 4096 is exact in
+// double and has at most 12 fractional digits).
+std::string q12_text(int q) {
+  std::ostringstream os;
+  os.precision(17);
+  os << q / 4096.0;
+  return os.str();
+}
+
 }  // namespace
+
+const char* combine_name(CombineKind k) {
+  static const char* names[] = {"add", "sub", "rsub", "absdiff", "min", "max", "lincomb", "above"};
+  return (int)k >= 0 && (int)k < (int)CombineKind::kCount ? names[(int)k] : "?";
+}
 
 const StencilInfo& stencil_info(StencilId id) {
   STRIPE_CHECK((int)id >= 0 && (int)id < (int)StencilId::kCount, "bad stencil id");
@@ -274,7 +288,100 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
       ops.insert(ops.end(), sub.begin(), sub.end());
       continue;
     }
-    if (name == "gray" || name == "grayscale" || name == "grey") {
+    // two-image sugar (filters.h): hold, the stencils with the token's @border, one combine op
+    {
+      const std::string suffix = op.has_border ? std::string("@") + border_name(op.border) : "";
+      std::string expansion;
+      for (const char* fam : {"gradient", "tophat", "blackhat"}) {
+        const std::string f = fam;
+        if (name.compare(0, f.size(), f) != 0) continue;
+        const std::string k = name.substr(f.size());
+        STRIPE_CHECK(k == "3" || k == "5",
+                     "'" << name << "': " << f << " takes a window size of 3 or 5 (" << f << "3, " << f << "5)");
+        STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << f << " takes no arguments");
+        if (f == "gradient") expansion = "hold,dilate" + k + suffix + ",swap,erode" + k + suffix + ",sub";
+        else if (f == "tophat") expansion = "hold,open" + k + suffix + ",sub";
+        else expansion = "hold,close" + k + suffix + ",rsub";
+      }
+      if (name == "unsharp") {
+        // unsharp[:S[:K]]  x + S (x - gaussianK(x)) in Q12: qa = -nearbyint(4096 S) on the blur, 4096 - qa on x
+        STRIPE_CHECK(parts.size() <= 3, "'" << tok << "': unsharp syntax: unsharp[:S[:K]]");
+        const double S = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 1.0;
+        const std::string k = parts.size() > 2 ? trim(parts[2]) : "5";
+        STRIPE_CHECK(S > 0.0 && S < 7.0, "'" << tok << "': unsharp amount must be in (0, 7)");
+        STRIPE_CHECK(k == "3" || k == "5" || k == "7", "'" << tok << "': unsharp blurs with gaussian3, 5 or 7");
+        const int qa = -(int)std::nearbyint(4096.0 * S);
+        STRIPE_CHECK(qa != 0 && 4096 - qa <= 32767, "'" << tok << "': unsharp amount must be in (0, 7)");
+        expansion = "hold,gaussian" + k + suffix + ",lincomb:" + q12_text(qa) + ":" + q12_text(4096 - qa);
+      }
+      if (name == "threshold" && parts.size() > 1 && trim(parts[1]) == "adaptive") {
+        // threshold:adaptive:K[:C]  x > boxK(x) - C
+        STRIPE_CHECK(parts.size() == 3 || parts.size() == 4,
+                     "'" << tok << "': adaptive threshold syntax: threshold:adaptive:K[:C]");
+        const std::string k = trim(parts[2]);
+        STRIPE_CHECK(k == "3" || k == "5", "'" << tok << "': threshold:adaptive takes a window size of 3 or 5");
+        const double Cd = parts.size() > 3 ? parse_num(trim(parts[3]), tok) : 0.0;
+        STRIPE_CHECK(Cd == std::nearbyint(Cd) && std::fabs(Cd) <= 255,
+                     "'" << tok << "': threshold:adaptive offset must be an integer in [-255, 255]");
+        expansion = "hold,box" + k + suffix + ",above:" + std::to_string((int)Cd);
+      }
+      if (!expansion.empty()) {
+        auto sub = parse_chain(expansion);
+        ops.insert(ops.end(), sub.begin(), sub.end());
+        continue;
+      }
+    }
+    if (name == "hold" || name == "save" || name == "swap") {
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
+      op.kind = name == "swap" ? OpKind::Swap : OpKind::Hold;
+      op.text = name == "swap" ? "swap" : "hold";
+    } else if (name == "add" || name == "sub" || name == "rsub" || name == "absdiff" || name == "min" ||
+               name == "max") {
+      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
+      op.kind = OpKind::Combine;
+      op.comb = name == "add"    ? CombineKind::Add
+                : name == "sub"  ? CombineKind::Sub
+                : name == "rsub" ? CombineKind::RSub
+                : name == "min"  ? CombineKind::Min
+                : name == "max"  ? CombineKind::Max
+                                 : CombineKind::AbsDiff;
+      op.text = name;
+    } else if (name == "lincomb" || name == "blend") {
+      // lincomb:a:b[:c] / blend:t  (Q12, filters.h); both spelled canonically as lincomb
+      op.kind = OpKind::Combine;
+      op.comb = CombineKind::LinComb;
+      if (name == "blend") {
+        STRIPE_CHECK(parts.size() == 2, "'" << tok << "': blend needs a weight, e.g. blend:0.25");
+        const double t = parse_num(trim(parts[1]), tok);
+        STRIPE_CHECK(t >= 0.0 && t <= 1.0, "'" << tok << "': blend weight must be in [0, 1]");
+        op.cq[0] = (int)std::nearbyint(4096.0 * t);
+        op.cq[1] = 4096 - op.cq[0];
+      } else {
+        STRIPE_CHECK(parts.size() == 3 || parts.size() == 4, "'" << tok << "': lincomb syntax: lincomb:a:b[:c]");
+        for (int i = 0; i < 2; ++i) {
+          const double a = parse_num(trim(parts[(size_t)i + 1]), tok);
+          const double q = std::nearbyint(a * 4096.0);
+          STRIPE_CHECK(std::fabs(q) <= 32767, "'" << tok << "': coefficient " << a << " out of range (|a| < 8)");
+          op.cq[i] = (int)q;
+        }
+        if (parts.size() == 4) {
+          const double c = parse_num(trim(parts[3]), tok);
+          STRIPE_CHECK(std::fabs(c) <= 2048, "'" << tok << "': offset " << c << " out of range (|c| <= 2048)");
+          op.cq[2] = (int)std::nearbyint(c * 4096.0);
+        }
+      }
+      op.text = "lincomb:" + q12_text(op.cq[0]) + ":" + q12_text(op.cq[1]) +
+                (op.cq[2] != 0 ? ":" + q12_text(op.cq[2]) : std::string());
+    } else if (name == "above") {
+      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': above syntax: above[:d]");
+      const double d = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 0.0;
+      STRIPE_CHECK(d == std::nearbyint(d) && std::fabs(d) <= 255,
+                   "'" << tok << "': above takes an integer offset in [-255, 255]");
+      op.kind = OpKind::Combine;
+      op.comb = CombineKind::Above;
+      op.ival = (int)d;
+      op.text = op.ival != 0 ? "above:" + std::to_string(op.ival) : std::string("above");
+    } else if (name == "gray" || name == "grayscale" || name == "grey") {
       op.kind = OpKind::Gray;
       op.gray = GrayMode::BT601;
       if (parts.size() > 1) {
@@ -448,10 +555,14 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
            "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
            "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
            "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv], "
-           "equalize, autocontrast[:P], threshold:otsu)");
+           "equalize, autocontrast[:P], threshold:otsu, "
+           "hold, swap, add, sub, rsub, absdiff, min, max, lincomb:a:b[:c], blend:t, above[:d], "
+           "gradient3/5, tophat3/5, blackhat3/5, unsharp[:S[:K]], threshold:adaptive:K[:C])");
     }
     STRIPE_CHECK(op.kind != OpKind::Stat || !op.has_border,
                  "'" << raw << "': " << op.text << " is a pointwise op and takes no @border");
+    STRIPE_CHECK(!(op.slot() || op.kind == OpKind::Combine) || !op.has_border,
+                 "'" << raw << "': " << op.text << " reads no border and takes no @border");
     if (op.has_border) op.text += std::string("@") + border_name(op.border);
     ops.push_back(op);
   }

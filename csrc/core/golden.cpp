@@ -101,9 +101,23 @@ Histogram golden_histogram(const Image& img) {
   return h;
 }
 
-void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1) {
+void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, ConstView in2) {
   STRIPE_CHECK(!p.pro.has_stat, "statistic op not resolved (resolve_stat) before the pass runs");
   if (y1 <= y0) return;
+  if (p.kind == PassKind::Combine) {
+    STRIPE_CHECK(in2.origin != nullptr, "combine pass without a held image");
+    const int64_t E = (int64_t)W * p.cin;
+    for (int y = y0; y < y1; ++y) {
+      const uint8_t* x = in.origin + (int64_t)y * in.pitch;
+      const uint8_t* h = in2.origin + (int64_t)y * in2.pitch;
+      uint8_t* dst = out.origin + (int64_t)y * out.pitch;
+      for (int64_t i = 0; i < E; ++i) {
+        const uint8_t v = combine_rule(p.comb, p.cq, p.cd, x[i], h[i]);
+        dst[i] = p.pro.has_post ? p.pro.post[v] : v;
+      }
+    }
+    return;
+  }
   if (p.kind == PassKind::Pointwise) {
     std::vector<uint8_t> o(3);
     for (int y = y0; y < y1; ++y) {
@@ -200,23 +214,49 @@ void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int
   }
 }
 
-Image golden_apply_plan(const Image& in, const Plan& plan) {
+Image golden_apply_plan(const Image& in, const Plan& plan, const Image* held_in) {
   STRIPE_CHECK(in.C == plan.cin, "image has " << in.C << " channels, chain expects " << plan.cin);
+  STRIPE_CHECK((plan.held_c != 0) == (held_in != nullptr), "the chain was compiled " << (plan.held_c ? "for" : "without")
+                                                               << " an external held image");
+  STRIPE_CHECK(!held_in || (held_in->W == in.W && held_in->H == in.H && held_in->C == plan.held_c),
+               "the held image must have the input's size and " << plan.held_c << " channel(s)");
   Image cur = in;
+  Image held = held_in ? *held_in : Image();
   for (const Pass& pp : plan.passes) {
+    for (char a : pp.slots) {
+      if (a == 'h') held = cur;
+      else std::swap(cur, held);
+    }
     // a statistic op: the table of this pass's input, the whole intermediate image
     const Pass p = pp.data_dependent() ? resolve_stat(pp, golden_histogram(cur)) : pp;
     Image nxt(in.W, in.H, p.cout);
     golden_pass(p, ConstView{cur.data.data(), cur.row_bytes()}, MutView{nxt.data.data(), nxt.row_bytes()},
-                in.W, RowGeom{0, in.H}, 0, in.H);
+                in.W, RowGeom{0, in.H}, 0, in.H, ConstView{held.data.data(), held.row_bytes()});
     cur = std::move(nxt);
   }
   return cur;
 }
 
-Image golden_apply_ops(const Image& in, const std::vector<Op>& ops, Border default_border) {
+Image golden_apply_ops(const Image& in, const std::vector<Op>& ops, Border default_border, const Image* held_in) {
   Image cur = in;
+  Image held = held_in ? *held_in : Image();
   for (const Op& op : ops) {
+    // two-image ops, straight from their rules (filters.h)
+    if (op.kind == OpKind::Hold) {
+      held = cur;
+      continue;
+    }
+    if (op.kind == OpKind::Swap || op.kind == OpKind::Combine) {
+      STRIPE_CHECK(held.C != 0, "'" << op.text << "': nothing is held (hold first)");
+      if (op.kind == OpKind::Swap) {
+        std::swap(cur, held);
+        continue;
+      }
+      STRIPE_CHECK(held.C == cur.C && held.W == cur.W && held.H == cur.H,
+                   "'" << op.text << "': the current image has " << cur.C << " channel(s), the held image " << held.C);
+      for (size_t i = 0; i < cur.data.size(); ++i) cur.data[i] = combine_u8(op, cur.data[i], held.data[i]);
+      continue;
+    }
     Plan one = compile_chain({op}, cur.C, default_border, /*fuse=*/false);
     cur = golden_apply_plan(cur, one);
   }

@@ -119,6 +119,28 @@ void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipSt
   // hipGetLastError is sticky per thread and libraries (RCCL) may leave benign
   // errors behind: clear it so the post-launch check reports only our launch
   (void)hipGetLastError();
+  if (p.kind == PassKind::Combine) {
+    // plain 64-bit row pointers (no descriptor views): the rows the kernel
+    // touches, whole 16-byte groups of [0, W * C), lie inside all three allocations
+    STRIPE_CHECK(L.in2 != nullptr && p.cin == p.cout && L.ext == 0, "bad combine launch");
+    const int64_t span = align_up((int64_t)L.W * p.cin, 16);
+    auto inside = [&](const uint8_t* org, const uint8_t* base, int64_t bytes, int64_t pitch) {
+      if (!base || org < base) return false;
+      for (int r = 0; r < L.nrange; ++r) {
+        const int y0 = L.ry[2 * r], y1 = L.ry[2 * r + 1];
+        if (y1 > y0 && (org - base) + (int64_t)(y1 - 1) * pitch + span > bytes) return false;
+      }
+      return true;
+    };
+    STRIPE_CHECK(inside(L.in, L.in_base, L.in_bytes, L.in_pitch) && inside(L.in2, L.in2_base, L.in2_bytes, L.in_pitch) &&
+                     inside(L.out, L.out_base, L.out_bytes, L.out_pitch),
+                 "combine rows outside their buffers");
+    STRIPE_CHECK(((uintptr_t)L.in | (uintptr_t)L.in2 | (uintptr_t)L.out) % 16 == 0 && L.in_pitch % 16 == 0 &&
+                     L.out_pitch % 16 == 0,
+                 "combine rows must be 16-byte aligned");
+    launch_combine(p, pc, L, s);
+    return;
+  }
   if (p.kind != PassKind::Pointwise && (L.in_bytes > desc_limit() || L.out_bytes > desc_limit())) {
     launch_chunked(p, pc, L, s);
     return;
@@ -128,6 +150,7 @@ void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipSt
     case PassKind::Separable:
     case PassKind::Direct: launch_stencil(p, pc, L, s); break;
     case PassKind::Conv: launch_conv(p, pc, L, s); break;
+    case PassKind::Combine: break;  // (launched above)
   }
 }
 

@@ -82,6 +82,12 @@ inline int env_nt_wgs() { return nt_wgs_knob().wgs; }
 constexpr int kKnobUnset = INT32_MIN;
 STRIPE_CACHED_KNOB(env_pw_wgs, int, env_int("STRIPE_PW_WGS", kKnobUnset))
 constexpr int kPwWgsFlat = 3, kPwWgsMix = 3, kPwWgsMixLut = 6;
+// Combine passes (k_combine), HBM-streaming launches: the flat passes' knob,
+// a cap of 2 workgroups per CU.  A workgroup keeps two input streams and one
+// output stream open, so fewer of them fill HBM's queues (16K RGB unsharp, six
+// interleaved rounds: 0.747-0.753 ms at 1, 0.655-0.668 at 2, 0.675-0.710 at 3,
+// 0.687-0.697 at 4, 0.699-0.717 uncapped; profiles/combine/README.md)
+constexpr int kPwWgsCombine = 2;
 
 // A/B knob, off: capping the resident workgroups of channel-changing passes
 // (STRIPE_PWG_WGS, LDS reservation) only slows them - 16K gray:ref 0.187 ms
@@ -170,6 +176,7 @@ enum class Family {
   PointwiseFlat,  // k_pointwise_flat
   ColorMix,       // k_colormix
   Blur,           // k_blur_pl
+  Combine,        // k_combine
 };
 
 struct PolicyIn {
@@ -284,6 +291,15 @@ inline StreamPolicy stream_policy(const PolicyIn& in) {
       if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;
       r.cap = env_pw_wgs() >= 0 ? env_pw_wgs() : (in.lut_stage ? kPwWgsMixLut : kPwWgsMix);
       r.cap_applied = r.cap > 0 && r.streaming && r.nt_stores;  // both: the size and the store policy
+      break;
+    }
+    case Family::Combine: {
+      // two inputs and one output of cin channels each: 3 bytes move per output byte
+      r.streaming = px * 3 * in.cin > dev::kNtMinBytes;
+      r.nt_stores = r.streaming;
+      if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
+      r.cap = env_pw_wgs() != kKnobUnset ? env_pw_wgs() : kPwWgsCombine;
+      r.cap_applied = r.cap > 0 && r.streaming && r.nt_stores;
       break;
     }
     case Family::Blur: {

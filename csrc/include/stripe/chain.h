@@ -47,7 +47,9 @@ struct PointwiseProgram {
   uint8_t apply_channel_lut(uint8_t v) const;  // post(pre(v)) when no gray
 };
 
-enum class PassKind : int { Pointwise = 0, Separable = 1, Direct = 2, Conv = 3 };
+// Combine: a two-input pointwise pass (current, held) -> new current image; its
+// `pro` holds at most a `post` table, the LUT-only run that followed the op.
+enum class PassKind : int { Pointwise = 0, Separable = 1, Direct = 2, Conv = 3, Combine = 4 };
 
 struct Pass {
   PassKind kind = PassKind::Pointwise;
@@ -74,9 +76,23 @@ struct Pass {
   // instead of LDS lookups
   bool post_aff = false;
   int post_a = 1, post_b = 0, post_k = 0;
+  // Combine: the op (filters.h combine_rule)
+  CombineKind comb = CombineKind::Add;
+  int cq[3] = {0, 0, 0};
+  int cd = 0;
+  // slot actions that precede the pass, in order: 'h' hold (the current image
+  // also becomes the held image), 's' swap (current and held exchange roles)
+  std::string slots;
+  // branched plans: the pass writes the x-margins of its input (R pixels, its
+  // border mode) before it reads them.  An image that more than one later op
+  // may read (held, swapped back in) has no single consumer whose margins its
+  // producer could maintain, so in a branched plan no producer maintains any
+  // (out_margin_px = 0 throughout) and every stencil fills its own.
+  bool fill_in = false;
   std::string desc;
   // the pass's LUT block is filled at run time from its input's histogram
   bool data_dependent() const { return pro.has_stat; }
+  bool branches() const { return !slots.empty() || kind == PassKind::Combine; }
 };
 
 struct Plan {
@@ -86,8 +102,22 @@ struct Plan {
   int max_channels = 3;
   int in_margin_px = 0;                      // margins the input must carry
   Border in_margin_border = Border::Reflect101;
+  int held_c = 0;  // channels of an external held image the chain starts with (0: none)
   std::vector<Pass> passes;
   std::string describe() const;
+  // some pass holds, swaps or combines: the engine keeps a third stripe buffer,
+  // and every schedule that assumes a static two-buffer chain declines
+  bool branched() const {
+    for (const Pass& p : passes)
+      if (p.branches()) return true;
+    return false;
+  }
+  // some pass holds or swaps (an external held image then cannot be iterated)
+  bool moves_slots() const {
+    for (const Pass& p : passes)
+      if (!p.slots.empty()) return true;
+    return false;
+  }
   // some pass carries a statistic op: every schedule that assumes a static
   // chain (deep halo, pipelined, graph replay, chunked transfers) declines
   bool data_dependent() const {
@@ -98,8 +128,9 @@ struct Plan {
 };
 
 // default_border: border for every stencil without an explicit @mode suffix.
+// held_c > 0: the chain starts with an external held image of that many channels.
 Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border,
-                   bool fuse = true);
+                   bool fuse = true, int held_c = 0);
 
 // The pass with its statistic op resolved against `h`, the histogram of the
 // pass's input over the WHOLE frame (p.cin channels): stat_lut's table composed

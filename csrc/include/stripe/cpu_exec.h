@@ -18,7 +18,9 @@ namespace stripe {
 int cpu_threads(int ranks_per_host = 1);
 
 // Compute output rows [y0, y1) (local) of one compiled pass on `threads` threads.
-void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads);
+// in2: the held image of a combine pass.
+void cpu_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, int threads,
+              ConstView in2 = {});
 
 // Histogram of rows [0, rows) of a W x C view (bytes of a row beyond W * C are
 // never read): row blocks on up to `threads` threads, one private table per
@@ -27,6 +29,6 @@ Histogram cpu_histogram(ConstView in, int W, int C, int rows, int threads);
 Histogram cpu_histogram(const Image& img, int threads);
 
 // Whole-image helper (like golden_apply_plan).
-Image cpu_apply_plan(const Image& in, const Plan& plan, int threads);
+Image cpu_apply_plan(const Image& in, const Plan& plan, int threads, const Image* held = nullptr);
 
 }  // namespace stripe

@@ -67,6 +67,9 @@ struct EngineConfig {
                                 // row and vice versa, a vertically periodic frame) -- the
                                 // per-step transfers of an N > 1 rank, measurable on one GPU.
                                 // Deep halo stays off; every halo schedule applies.
+  bool held_input = false;      // the chain starts with an external held image (cin channels,
+                                // Engine::load_held_packed): the two-tensor form of the
+                                // combine ops.  Single-process engines only
   bool graphs = false;          // replay iterated chains from a captured hipGraph when a run()
                                 // involves no collective (single rank, or no halo exchange).
                                 // Off by default: measured on MI355X/ROCm 7, graph replay of
@@ -155,6 +158,8 @@ class Engine {
   // ---- input ----
   void load_synthetic(uint64_t seed);                     // own stripe, generated in place
   void load_packed(const void* src, bool src_device);     // own stripe, packed rows
+  // own stripe of the external held image (EngineConfig::held_input), packed rows of cin channels
+  void load_held_packed(const void* src, bool src_device);
   void load_root(const void* full, bool src_device);      // rank 0: full frame into root buffer
   // rank 0: a baseline JPEG's entropy-decoded coefficients into the root
   // buffer; a device engine runs IDCT / upsampling / colour on the GPU
@@ -352,7 +357,16 @@ class Engine {
   bool self_halo_ = false;  // EngineConfig::self_halo, validated
   bool time_halo_ = true;  // record the halo stage events (last iteration of a run only)
   bool stage_timing_ = true;  // set_stage_timing
-  void run_pass(const Pass& p, const uint8_t* in, uint8_t* out);
+  void run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint8_t* in2 = nullptr);
+  // One pass of the chain on the engine's buffers: the pass's slot actions
+  // (hold / swap: index changes), the pass from the current buffer (and the
+  // held one) into a free buffer, which becomes current.
+  void step_pass(const Pass& p);
+  // the buffer a pass writes: the other one of the ping-pong pair, or (branched
+  // plans) the one that is neither current nor held
+  int free_buf() const;
+  void apply_slots(const Pass& p);
+  void reset_held() { held_ = ext_held_ ? 2 : -1; }  // the held slot at the start of an iteration
   // Statistic passes (Pass::data_dependent).  Before such a pass runs, on the
   // compute stream: the histogram of its input stripe, the all-reduce over the
   // active ranks (every active rank runs every pass, so none waits for a rank
@@ -395,7 +409,9 @@ class Engine {
   Partition part_;
   int halo_ = 0;            // halo rows allocated above/below the stripe
   int rows_alloc_ = 0;
-  Buffer buf_[2];
+  Buffer buf_[3];           // the ping-pong pair; [2] only for branched plans (Plan::branched)
+  int held_ = -1;           // which buffer holds the held image (-1: none)
+  bool ext_held_ = false;   // buf_[2] holds the external held image (load_held_packed)
   int cur_ = 0;             // which buffer holds the current input
   int cur_c_ = 3;           // channels of the current input
   Buffer zero_;             // one all-zero padded row (Constant y-border)
@@ -406,7 +422,7 @@ class Engine {
   std::vector<hipEvent_t> ev_h2d_, ev_cmp_;
   PinnedBuffer host_in_, host_out_;
   Buffer stage_in_, stage_out_;  // packed device staging rows of the e2e path
-  PassLaunch make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi) const;
+  PassLaunch make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi, const uint8_t* in2 = nullptr) const;
   bool own_streams_ = false;   // s_comm_ (and the e2e streams) are ours
   bool own_compute_ = false;   // s_compute_ is ours (false after use_external_stream)
   hipEvent_t ev_[8] = {};

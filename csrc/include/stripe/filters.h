@@ -44,6 +44,35 @@
 //                 (double)n0 (double)S, in IEEE double without contraction;
 //                 T = the smallest t that attains the maximum (one grey
 //                 level: T = 1).
+//
+// Two-image ops.  X is the current image, H the held image (same channel count);
+// every rule is per byte.  Slot ops move no pixels:
+//   hold (save)   the current image also becomes the held image (a second hold
+//                 replaces the first)
+//   swap          current and held exchange roles
+// Combine ops (OpKind::Combine, combine_u8) read X and H and write a new current
+// image; H stays held:
+//   add           min(255, X + H)
+//   sub           max(0, H - X)            (held minus current)
+//   rsub          max(0, X - H)
+//   absdiff       |X - H|
+//   min, max      byte minimum / maximum
+//   lincomb:a:b[:c]  sat_u8((qa X + qb H + qc + 2048) >> 12), >> = floor, with
+//                 qa = nearbyint(4096 a), qb = nearbyint(4096 b), |q| <= 32767,
+//                 qc = nearbyint(4096 c), |c| <= 2048: the colour matrix's Q12
+//                 rule and ranges; the sum fits 26 bits
+//   blend:t       lincomb with qa = nearbyint(4096 t), qb = 4096 - qa, 0 <= t <= 1
+//                 (equal images are fixed points)
+//   above[:d]     H - X + d > 0 ? 255 : 0, integer d in [-255, 255], default 0
+// Parser sugar (an @border suffix goes to the stencils inside):
+//   gradient3/5   hold,dilateK,swap,erodeK,sub
+//   tophat3/5     hold,openK,sub
+//   blackhat3/5   hold,closeK,rsub
+//   unsharp[:S[:K]]  hold,gaussianK,lincomb with qa = -nearbyint(4096 S),
+//                 qb = 4096 - qa; S defaults to 1 (0 < S < 7), K in {3,5,7}
+//                 defaults to 5; flat regions are fixed points
+//   threshold:adaptive:K[:C]  hold,boxK,above:C, K in {3,5}, C defaults to 0:
+//                 OpenCV's ADAPTIVE_THRESH_MEAN_C on boxK's own rounding
 #pragma once
 
 #include <array>
@@ -65,7 +94,13 @@ enum class OpKind : int {
   Conv,     // float KxK convolution (blur:K, conv:...), MFMA path on GPU
   ColorMatrix,  // 3 -> 3 channels: out_c = sat((sum_k q[c][k] p_k + qb[c] + 2048) >> 12)
   Stat,     // per-byte table built at run time from the global histogram (Op::stat)
+  Hold,     // slot op: the current image also becomes the held image
+  Swap,     // slot op: current and held exchange roles
+  Combine,  // two-input pointwise op on (current, held) (Op::comb)
 };
+
+enum class CombineKind : int { Add = 0, Sub, RSub, AbsDiff, Min, Max, LinComb, Above, kCount };
+const char* combine_name(CombineKind k);
 
 enum class StatKind : int { Equalize = 0, AutoContrast = 1, Otsu = 2 };
 
@@ -139,6 +174,8 @@ struct Op {
   StatKind stat = StatKind::Equalize;  // OpKind::Stat
   StencilId sid = StencilId::Gaussian5;
   int cm[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // colour matrix: q row-major, then qb (kColorShift)
+  CombineKind comb = CombineKind::Add;  // OpKind::Combine
+  int cq[3] = {0, 0, 0};                // lincomb / blend: qa, qb, qc (kColorShift); above: d in ival
   int K = 0;                  // conv window
   std::vector<float> weights; // conv: K*K f32 weights
   std::vector<float> sep_h, sep_v;  // conv: 1-D factors when weights[dy][dx] = sep_v[dy] * sep_h[dx]
@@ -151,6 +188,7 @@ struct Op {
   Border border = Border::Reflect101;
 
   bool pointwise() const { return kind != OpKind::Stencil && kind != OpKind::Conv; }
+  bool slot() const { return kind == OpKind::Hold || kind == OpKind::Swap; }
   int radius() const;
   int channels_out(int cin) const;
 };
@@ -166,6 +204,28 @@ inline uint8_t color_matrix_channel(const int* cm, int c, int r, int g, int b) {
                 kColorShift;  // arithmetic shift: floor
   return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
+
+// Combine arithmetic (rules at the top of this file; the one definition every
+// layer calls): byte x of the current image, byte h of the held image.
+inline uint8_t combine_rule(CombineKind k, const int* cq, int d, uint8_t x, uint8_t h) {
+  const int X = x, H = h;
+  int v = 0;
+  switch (k) {
+    case CombineKind::Add: v = X + H; break;
+    case CombineKind::Sub: v = H - X; break;
+    case CombineKind::RSub: v = X - H; break;
+    case CombineKind::AbsDiff: v = X > H ? X - H : H - X; break;
+    case CombineKind::Min: v = X < H ? X : H; break;
+    case CombineKind::Max: v = X > H ? X : H; break;
+    case CombineKind::LinComb:
+      v = (cq[0] * X + cq[1] * H + cq[2] + (1 << (kColorShift - 1))) >> kColorShift;  // arithmetic shift: floor
+      break;
+    case CombineKind::Above: return H - X + d > 0 ? 255 : 0;
+    default: break;
+  }
+  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+inline uint8_t combine_u8(const Op& op, uint8_t x, uint8_t h) { return combine_rule(op.comb, op.cq, op.ival, x, h); }
 
 // Statistic ops (rules at the top of this file): the table of `op`
 // (OpKind::Stat) for an image with histogram `h` (channels pooled), and Otsu's

@@ -33,16 +33,19 @@ struct RowGeom {
   int Hg = 0;
 };
 
-// Compute output rows [y0, y1) (local) of one compiled pass.
-void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1);
+// Compute output rows [y0, y1) (local) of one compiled pass.  in2: the held
+// image of a combine pass (PassKind::Combine), same channels as `in`.
+void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int y0, int y1, ConstView in2 = {});
 
 // 256 x C counts of exactly the frame's W x H pixels.
 Histogram golden_histogram(const Image& img);
 
 // Whole-image helpers.  A pass that carries a statistic op (Pass::data_dependent)
 // is resolved against the histogram of the intermediate image it reads.
-Image golden_apply_plan(const Image& in, const Plan& plan);
+// held: the external held image of a plan compiled with held_c > 0.
+Image golden_apply_plan(const Image& in, const Plan& plan, const Image* held = nullptr);
 // Unfused: one op at a time (checks the chain compiler's fusion is exact).
-Image golden_apply_ops(const Image& in, const std::vector<Op>& ops, Border default_border);
+Image golden_apply_ops(const Image& in, const std::vector<Op>& ops, Border default_border,
+                       const Image* held = nullptr);
 
 }  // namespace stripe

@@ -44,6 +44,11 @@ struct PassLaunch {
   int64_t in_pitch = 0;
   uint8_t* out = nullptr;        // origin of the output stripe
   int64_t out_pitch = 0;
+  // combine passes: origin of the held image's stripe (pitch in_pitch) and the
+  // allocation it lies in (checked by launch_pass)
+  const uint8_t* in2 = nullptr;
+  const uint8_t* in2_base = nullptr;
+  int64_t in2_bytes = 0;
   int W = 0;                     // pixels per row
   int rows = 0;                  // local rows owned
   int row0 = 0, Hg = 0;          // border geometry (global row of local 0, global H)
@@ -85,6 +90,8 @@ void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipSt
 void launch_pointwise(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 void launch_conv(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
+// Two-input pointwise pass (csrc/hip/combine.hip k_combine): out = post(op(in, in2)).
+void launch_combine(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s);
 
 // Histogram of rows [0, rows) of a stripe (csrc/hip/histogram.hip k_hist): a
 // read-only pass that ADDS the counts of exactly the rows' W * C bytes (no

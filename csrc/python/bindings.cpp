@@ -233,8 +233,21 @@ PYBIND11_MODULE(_C, m) {
   m.def("describe_chain", [](const std::string& chain, int cin, const std::string& border, bool fuse) {
     return compile_chain(parse_chain(chain), cin, parse_border(border), fuse).describe();
   }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true);
-  m.def("plan_info", [](const std::string& chain, int cin, const std::string& border, bool fuse) {
-    Plan p = compile_chain(parse_chain(chain), cin, parse_border(border), fuse);
+  m.def("combine_u8", [](const std::string& token, const U8Array& x, const U8Array& h) {
+    // one combine token (add, sub, ..., lincomb:a:b[:c], blend:t, above[:d]) on two equal-shaped arrays
+    auto ops = parse_chain(token);
+    STRIPE_CHECK(ops.size() == 1 && ops[0].kind == OpKind::Combine, "'" << token << "' is not one combine op");
+    STRIPE_CHECK(x.size() == h.size(), "combine_u8: the arrays differ in size");
+    U8Array out(std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
+    const uint8_t* px = x.data();
+    const uint8_t* ph = h.data();
+    uint8_t* po = out.mutable_data();
+    for (py::ssize_t i = 0; i < x.size(); ++i) po[i] = combine_u8(ops[0], px[i], ph[i]);
+    return out;
+  }, py::arg("token"), py::arg("x"), py::arg("h"),
+        "combine_u8 (filters.h) per byte: x the current image's bytes, h the held image's");
+  m.def("plan_info", [](const std::string& chain, int cin, const std::string& border, bool fuse, int held_channels) {
+    Plan p = compile_chain(parse_chain(chain), cin, parse_border(border), fuse, held_channels);
     py::dict d;
     d["cin"] = p.cin;
     d["cout"] = p.cout;
@@ -254,12 +267,21 @@ PYBIND11_MODULE(_C, m) {
       q["out_margin_px"] = ps.out_margin_px;
       q["cmat"] = ps.pro.cmat;
       q["stat"] = ps.pro.has_stat ? ps.pro.stat.text : std::string();  // statistic op leading the program
+      // two-image plans: the slot actions in front of the pass, a combine pass's op and folded table
+      py::list slots;
+      for (char a : ps.slots) slots.append(a == 'h' ? "hold" : "swap");
+      q["slots"] = slots;
+      q["combine"] = ps.kind == PassKind::Combine ? std::string(combine_name(ps.comb)) : std::string();
+      q["post_lut"] = ps.kind == PassKind::Combine && ps.pro.has_post;
+      q["fill_in"] = ps.fill_in;
       passes.append(q);
     }
     d["passes"] = passes;
     d["data_dependent"] = p.data_dependent();
+    d["branched"] = p.branched();
     return d;
-  }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true);
+  }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true,
+     py::arg("held_channels") = 0);
 
   // ---- launch policy (csrc/hip/launch_policy.h: pure host functions, no GPU) ----
   m.def("launch_policy", [](const std::string& family, int cin, int cout, int cmid, int W, int rows, int nt, int wgs,
@@ -269,7 +291,7 @@ PYBIND11_MODULE(_C, m) {
         {"direct", policy::Family::Direct},     {"rank", policy::Family::Rank},
         {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
-        {"blur", policy::Family::Blur}};
+        {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine}};
     const policy::Family* f = nullptr;
     for (const auto& n : names)
       if (family == n.first) f = &n.second;
@@ -296,42 +318,55 @@ PYBIND11_MODULE(_C, m) {
      py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
      py::arg("lut_stage") = false,
      "the launch decision of a kernel family: sep | sobel_rp | direct | rank | conv_small | pointwise | "
-     "pointwise_flat | colormix | blur");
+     "pointwise_flat | colormix | blur | combine");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));
 
   // ---- golden ----
-  m.def("golden_apply", [](const U8Array& a, const std::string& chain, const std::string& border, bool fuse) {
+  // held: a second image of the same shape, the external held image of the chain (None: none)
+  m.def("golden_apply", [](const U8Array& a, const std::string& chain, const std::string& border, bool fuse,
+                           py::object held) {
     Image img = image_from_numpy(a);
+    Image himg;
+    if (!held.is_none()) himg = image_from_numpy(held.cast<U8Array>());
+    const bool has_held = !held.is_none();
     Image out;
     {
       py::gil_scoped_release nogil;
-      Plan p = compile_chain(parse_chain(chain), img.C, parse_border(border), fuse);
-      out = golden_apply_plan(img, p);
-    }
-    return image_to_numpy(out);
-  }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101", py::arg("fuse") = true);
-  m.def("cpu_apply", [](const U8Array& a, const std::string& chain, const std::string& border, bool fuse,
-                        int threads) {
-    Image img = image_from_numpy(a);
-    Image out;
-    {
-      py::gil_scoped_release nogil;
-      Plan p = compile_chain(parse_chain(chain), img.C, parse_border(border), fuse);
-      out = cpu_apply_plan(img, p, threads > 0 ? threads : cpu_threads());
+      Plan p = compile_chain(parse_chain(chain), img.C, parse_border(border), fuse, has_held ? himg.C : 0);
+      out = golden_apply_plan(img, p, has_held ? &himg : nullptr);
     }
     return image_to_numpy(out);
   }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101", py::arg("fuse") = true,
-     py::arg("threads") = 0);
-  m.def("golden_apply_unfused", [](const U8Array& a, const std::string& chain, const std::string& border) {
+     py::arg("held") = py::none());
+  m.def("cpu_apply", [](const U8Array& a, const std::string& chain, const std::string& border, bool fuse,
+                        int threads, py::object held) {
     Image img = image_from_numpy(a);
+    Image himg;
+    if (!held.is_none()) himg = image_from_numpy(held.cast<U8Array>());
+    const bool has_held = !held.is_none();
     Image out;
     {
       py::gil_scoped_release nogil;
-      out = golden_apply_ops(img, parse_chain(chain), parse_border(border));
+      Plan p = compile_chain(parse_chain(chain), img.C, parse_border(border), fuse, has_held ? himg.C : 0);
+      out = cpu_apply_plan(img, p, threads > 0 ? threads : cpu_threads(), has_held ? &himg : nullptr);
     }
     return image_to_numpy(out);
-  }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101");
+  }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101", py::arg("fuse") = true,
+     py::arg("threads") = 0, py::arg("held") = py::none());
+  m.def("golden_apply_unfused", [](const U8Array& a, const std::string& chain, const std::string& border,
+                                   py::object held) {
+    Image img = image_from_numpy(a);
+    Image himg;
+    if (!held.is_none()) himg = image_from_numpy(held.cast<U8Array>());
+    const bool has_held = !held.is_none();
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_apply_ops(img, parse_chain(chain), parse_border(border), has_held ? &himg : nullptr);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101", py::arg("held") = py::none());
 
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
@@ -670,6 +705,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("root_buffers", &EngineConfig::root_buffers)
       .def_readwrite("autotune", &EngineConfig::autotune)
       .def_readwrite("graphs", &EngineConfig::graphs)
+      .def_readwrite("held_input", &EngineConfig::held_input)
       .def_readwrite("self_halo", &EngineConfig::self_halo)
       .def_readwrite("cold", &EngineConfig::cold)
       .def_readwrite("pipeline", &EngineConfig::pipeline)
@@ -752,6 +788,16 @@ PYBIND11_MODULE(_C, m) {
         STRIPE_CHECK((size_t)a.size() == (size_t)e.stripe().rows * e.config().W * e.config().C,
                      "stripe array has the wrong size");
         e.load_packed(a.data(), false);
+        e.synchronize();
+      })
+      .def("load_held_packed_ptr", [](Engine& e, uintptr_t p, bool dev) {
+        py::gil_scoped_release nogil;
+        e.load_held_packed(reinterpret_cast<const void*>(p), dev);
+      })
+      .def("load_held_packed", [](Engine& e, const U8Array& a) {
+        STRIPE_CHECK((size_t)a.size() == (size_t)e.stripe().rows * e.config().W * e.config().C,
+                     "held stripe array has the wrong size");
+        e.load_held_packed(a.data(), false);
         e.synchronize();
       })
       .def("load_root", [](Engine& e, const U8Array& a) {

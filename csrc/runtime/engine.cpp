@@ -99,7 +99,9 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
     STRIPE_CHECK(comm_->device_buffers() == device(),
                  "comm backend '" << comm_->backend() << "' does not match the engine backend");
   }
-  plan_ = compile_chain(parse_chain(cfg_.chain), cfg_.C, cfg_.border, cfg_.fuse);
+  STRIPE_CHECK(!cfg_.held_input || world_ == 1,
+               "held_input (an external held image) needs a single-process engine, got " << world_ << " ranks");
+  plan_ = compile_chain(parse_chain(cfg_.chain), cfg_.C, cfg_.border, cfg_.fuse, cfg_.held_input ? cfg_.C : 0);
   if (cfg_.row_weights.empty()) {
     part_ = plan_rows(cfg_.H, world_, std::max(1, plan_.max_radius), cfg_.legacy_partition);
   } else {
@@ -135,7 +137,9 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   }
   // one extra all-zero row at the end of each stripe buffer: the Constant
   // y-border row the buffer-descriptor kernels read (never written)
-  for (auto& b : buf_) b = Buffer((size_t)(std::max(1, rows_alloc_) + 1) * pmax, device());
+  // (the third buffer, for the held image, only where the plan branches: half as much stripe memory again)
+  for (int i = 0; i < (plan_.branched() || cfg_.held_input ? 3 : 2); ++i)
+    buf_[i] = Buffer((size_t)(std::max(1, rows_alloc_) + 1) * pmax, device());
   zero_ = Buffer((size_t)pmax, device());
   if (cfg_.root_buffers && rank_ == 0) {
     root_in_ = Buffer((size_t)cfg_.H * padded_pitch(cfg_.W, plan_.cin), device());
@@ -427,6 +431,20 @@ void Engine::load_packed(const void* src, bool src_device) {
   cur_c_ = C;
 }
 
+void Engine::load_held_packed(const void* src, bool src_device) {
+  (void)src_device;
+  STRIPE_CHECK(cfg_.held_input, "load_held_packed needs EngineConfig::held_input");
+  settle_post();
+  const int C = plan_.held_c;
+  const int64_t E = (int64_t)cfg_.W * C;
+  TraceRange tr("stripe.load");
+  // no margins: a combine pass reads none, and a stencil that reads the image
+  // after a swap fills its own (Pass::fill_in)
+  copy2d(origin(buf_[2], C), pitch(C), src, E, E, stripe().rows, s_compute_, 0);
+  ext_held_ = true;
+  held_ = 2;
+}
+
 void Engine::load_root(const void* full, bool src_device) {
   (void)src_device;
   if (rank_ != 0) return;
@@ -472,6 +490,7 @@ void Engine::load_root_synthetic(uint64_t seed) {
 }
 
 void Engine::scatter() {
+  STRIPE_CHECK(!cfg_.held_input, "scatter: an external held image (held_input) is loaded per engine, not scattered");
   settle_post();
   deep_phase_ = 0;
   const int C = plan_.cin;
@@ -580,7 +599,7 @@ void Engine::post_halo_ops(uint8_t* org, int C, int R, hipStream_t s) {
 
 bool Engine::posts_halo() const {
   return device() && comm_ && cfg_.halo && neighbours() && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
-         plan_.passes[0].R > 0 && stripe().rows > 0 && !plan_.data_dependent();
+         plan_.passes[0].R > 0 && stripe().rows > 0 && !plan_.data_dependent() && !plan_.branched();
 }
 
 void Engine::post_halo() {
@@ -639,7 +658,7 @@ void Engine::run_posted() {
   halo_done_ = false;
 }
 
-PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi) const {
+PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi, const uint8_t* in2) const {
   const RowGeom g = geom();
   PassLaunch L;
   L.in = in;
@@ -659,13 +678,23 @@ PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, i
   L.nt = prt_[pi].nt >= 0 ? prt_[pi].nt : (cfg_.cold ? 1 : -1);
   const Buffer* bi = nullptr;
   const Buffer* bo = nullptr;
-  // the ping-pong pair, or the root's full-frame buffers (one-rank run_dist)
-  for (const Buffer* b : {&buf_[0], &buf_[1], &root_in_, &root_out_}) {
+  const Buffer* b2 = nullptr;
+  // the ping-pong pair (with the held image's buffer: three), or the root's
+  // full-frame buffers (one-rank run_dist)
+  for (const Buffer* b : {&buf_[0], &buf_[1], &buf_[2], &root_in_, &root_out_}) {
     if (!b->data()) continue;
     if (in >= b->data() && in < b->data() + b->bytes()) bi = b;
     if (out >= b->data() && out < b->data() + b->bytes()) bo = b;
+    if (in2 && in2 >= b->data() && in2 < b->data() + b->bytes()) b2 = b;
   }
   STRIPE_CHECK(bi && bo && bi != bo, "pass buffers are not the engine's ping-pong pair");
+  STRIPE_CHECK((p.kind == PassKind::Combine) == (in2 != nullptr), "a combine pass, and only it, reads a held image");
+  if (in2) {
+    STRIPE_CHECK(b2 && b2 != bo, "the held image is not in one of the engine's buffers, or in the output's");
+    L.in2 = in2;
+    L.in2_base = b2->data();
+    L.in2_bytes = (int64_t)b2->bytes();
+  }
   L.in_base = bi->data();
   L.in_bytes = (int64_t)bi->bytes();
   L.in_org = in - bi->data();
@@ -679,10 +708,48 @@ PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, i
   return L;
 }
 
-void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
+int Engine::free_buf() const {
+  if (!buf_[2].data()) return cur_ ^ 1;
+  for (int i = 0; i < 3; ++i)
+    if (i != cur_ && i != held_) return i;
+  return cur_ ^ 1;  // (not reached: three buffers, two of them taken)
+}
+
+void Engine::apply_slots(const Pass& p) {
+  for (char a : p.slots) {
+    if (a == 'h') {
+      held_ = cur_;
+    } else {
+      STRIPE_CHECK(held_ >= 0, "swap with nothing held");
+      std::swap(cur_, held_);
+    }
+  }
+}
+
+void Engine::step_pass(const Pass& p) {
+  apply_slots(p);
+  const int o = free_buf();
+  const uint8_t* in2 = nullptr;
+  if (p.kind == PassKind::Combine) {
+    STRIPE_CHECK(held_ >= 0, "combine pass with nothing held" << (cfg_.held_input ? " (load_held_packed first)" : ""));
+    in2 = origin(buf_[held_], p.cin);
+  }
+  run_pass(p, origin(buf_[cur_], p.cin), origin(buf_[o], p.cout), in2);
+  cur_ = o;
+}
+
+void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint8_t* in2) {
   const Stripe& st = stripe();
   const int rows = st.rows;
   if (rows == 0) return;
+  if (p.fill_in && device()) {
+    // branched plans: the stencil writes its input's x-margins itself, before
+    // the halo exchange ships these rows (lazily completed sends of an earlier
+    // pass may still read them)
+    if (comm_) comm_->flush_sends();
+    fill_margins(const_cast<uint8_t*>(in), p.cin, 0, rows, p.R, p.border == Border::Skip ? Border::Reflect101 : p.border,
+                 s_compute_);
+  }
   // a statistic op: the table of this pass's input over all active ranks, in
   // the pass's LUT block (device) / in the resolved pass (host)
   Pass resolved;
@@ -713,12 +780,12 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
   if (!device()) {
     if (xchg) exchange_halo(const_cast<uint8_t*>(in), p.cin, R, nullptr);
     cpu_pass(p.data_dependent() ? resolved : p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, g, 0,
-             rows, host_threads());
+             rows, host_threads(), ConstView{in2, pitch(p.cin)});
     return;
   }
   const size_t pi = (size_t)(&p - plan_.passes.data());
   const PassConsts& pc = prt_[pi].pc;
-  PassLaunch L = make_launch(p, in, out, (int)pi);
+  PassLaunch L = make_launch(p, in, out, (int)pi, in2);
   if (!xchg) {
     L.nrange = 1;
     L.ry[0] = 0;
@@ -768,6 +835,7 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out) {
 bool Engine::graph_ok() const {
   if (!device() || !cfg_.graphs) return false;
   if (plan_.data_dependent()) return false;  // a statistic pass synchronises and may reduce over the ranks
+  if (plan_.branched()) return false;        // three buffers: the two-buffer replay cycle does not hold
   const bool comm = cfg_.halo && plan_.max_radius > 0 && neighbours();
   return !comm && stripe().rows > 0;
 }
@@ -778,6 +846,8 @@ void Engine::run(int iterations) {
   if (cfg_.autotune && !tuned_) autotune_bands();
   STRIPE_CHECK(iterations == 1 || plan_.cout == plan_.cin,
                "iterating a chain needs equal input/output channels (" << plan_.cin << "->" << plan_.cout << ")");
+  STRIPE_CHECK(!(cfg_.held_input && iterations > 1 && plan_.moves_slots()),
+               "iterating a chain with an external held image needs a chain without hold or swap");
   TraceRange tr("stripe.compute");
   fault_point("compute", rank_);
   stage_begin(Stage::Compute, s_compute_);
@@ -786,10 +856,8 @@ void Engine::run(int iterations) {
     for (int it = 0; it < n; ++it) {
       time_halo_ = it == n - 1;  // two event records per exchange: only where they are read
       STRIPE_CHECK(cur_c_ == plan_.cin, "engine input has " << cur_c_ << " channels, chain expects " << plan_.cin);
-      for (const Pass& p : plan_.passes) {
-        run_pass(p, origin(buf_[cur_], p.cin), origin(buf_[cur_ ^ 1], p.cout));
-        cur_ ^= 1;
-      }
+      reset_held();  // the held slot is empty (or holds the external image) as an iteration starts
+      for (const Pass& p : plan_.passes) step_pass(p);
       cur_c_ = plan_.cout;
     }
   };
@@ -839,6 +907,9 @@ void Engine::run(int iterations) {
     iterate(iterations);
   }
   if (comm_) comm_->flush_sends();  // every lazily completed send of this run
+  // a chain that holds or swaps may have written or renamed the buffer of the
+  // external held image: it is spent, and the next run needs load_held_packed again
+  if (plan_.moves_slots()) ext_held_ = false;
   stage_end(Stage::Compute, s_compute_);
   time_halo_ = true;
   out_buf_ = cur_;

@@ -209,6 +209,9 @@ namespace {
 Image run_rank_impl(const EngineConfig& cfg_in, Comm* comm, int device, const Image* input, const JpegCoefs* jpeg,
                     int iterations, PhaseTimes* times, JpegOut* jpeg_out) {
   const int rank = comm ? comm->rank() : 0;
+  STRIPE_CHECK(!cfg_in.held_input,
+               "an external held image (held_input) is loaded into a single-process engine "
+               "(Engine::load_held_packed); the scatter / gather pipeline has no path for it");
   EngineConfig c = cfg_in;
   // the root knows the geometry (it read the image); everyone else learns it
   // from the metadata broadcast

@@ -36,6 +36,7 @@ namespace stripe {
 // ---------------------------------------------------------------------------
 bool Engine::pipelined_ok() const {
   if (plan_.data_dependent()) return false;  // statistic passes take the plain per-pass path
+  if (plan_.branched()) return false;        // so do chains with a held image (three buffers)
   if (device() && schedule_emu() == 2 && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
       stripe().rows > 4 * plan_.passes[0].R && plan_.passes[0].R > 0)
     return true;
@@ -144,6 +145,8 @@ int Engine::chain_reach() const {
   // a statistic pass needs the histogram of its whole input before it runs: no
   // deep halo, no deep steps (the recomputed neighbour rows would need it too)
   if (plan_.data_dependent()) return 0;
+  // a held image: the deep schedules walk a static two-buffer chain
+  if (plan_.branched()) return 0;
   int s = 0;
   for (const Pass& p : plan_.passes) {
     if (p.kind != PassKind::Pointwise && p.kind != PassKind::Separable && p.kind != PassKind::Direct) return 0;

@@ -68,7 +68,7 @@ Histogram Engine::stripe_histogram(const uint8_t* org, int C) {
   L.W = cfg_.W;
   L.C = C;
   L.rows = st.rows;
-  for (const Buffer* b : {&buf_[0], &buf_[1]})
+  for (const Buffer* b : {&buf_[0], &buf_[1], &buf_[2]})
     if (b->data() && org >= b->data() && org < b->data() + b->bytes()) {
       L.in_base = b->data();
       L.in_bytes = (int64_t)b->bytes();

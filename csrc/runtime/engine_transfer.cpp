@@ -125,7 +125,7 @@ void Engine::run_e2e(int chunks) {
   }
   stage_end(Stage::H2D, s_h2d_);
   // (a statistic pass needs its whole input before it runs: unpipelined too)
-  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent();
+  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent() && !plan_.branched();
   if (!single) {
     // multi-pass chains: upload overlapped with nothing but the download of the
     // previous step; the chain itself runs as usual
@@ -233,6 +233,7 @@ void Engine::join_d2h() {
 int Engine::dist_chunks(int chunks) const {
   if (!comm_ || part_.active <= 1 || chunks < 2 || plan_.passes.size() != 1) return 0;
   if (plan_.data_dependent()) return 0;  // the table needs the whole frame: scatter, run, gather
+  if (plan_.branched()) return 0;        // a held image: scatter, run, gather
   const Pass& p = plan_.passes[0];
   if (p.kind != PassKind::Separable && p.kind != PassKind::Direct && p.kind != PassKind::Pointwise) return 0;
   if (cfg_.halo && p.R > halo_) return 0;
@@ -246,6 +247,7 @@ bool Engine::dist_direct() const {
   if (!device() || part_.active != 1 || rank_ != 0 || plan_.passes.size() != 1) return false;
   if (!root_in_.data() || !root_out_.data()) return false;
   if (plan_.data_dependent()) return false;  // prepare_stat reads the stripe buffers
+  if (plan_.branched()) return false;        // the held image lives in the stripe buffers
   const Pass& p = plan_.passes[0];
   return p.kind == PassKind::Separable || p.kind == PassKind::Direct || p.kind == PassKind::Pointwise;
 }
@@ -473,7 +475,7 @@ void Engine::run_to_host(void* dst, int chunks) {
   stage_begin(Stage::E2E, s_compute_);
   const Pass& p0 = plan_.passes[0];
   // any kind: launch_pass takes row ranges (a statistic pass goes through run())
-  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent();
+  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent() && !plan_.branched();
   if (!single) {  // multi-pass chains: the chain, then the download
     run(1);
     const int ob = out_buf_;

@@ -132,7 +132,9 @@ void Engine::autotune_bands() {
     // it stands -- the static table, an identity statistic -- and without its
     // histogram or all-reduce: the candidate loops differ per rank unless the
     // tune is reduced, so a collective inside them would deadlock)
-    PassLaunch L = make_launch(p, origin(buf_[cur_], p.cin), origin(buf_[cur_ ^ 1], p.cout), (int)i);
+    // (a branched plan: any buffer but the current one takes the scratch output;
+    // its combine passes are not tuned, they launch with whatever the buffers hold)
+    PassLaunch L = make_launch(p, origin(buf_[cur_], p.cin), origin(buf_[cur_ == 0 ? 1 : 0], p.cout), (int)i);
     L.ry[0] = 0;
     L.ry[1] = L.rows;
     auto launch_one = [&]() {

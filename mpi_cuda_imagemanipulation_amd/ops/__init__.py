@@ -72,6 +72,23 @@ FILTERS = {
     "conv:K:w0;w1;...[:lsb]": "generic KxK float correlation (MFMA path); :lsb = within 1 LSB, 2/3 of the MFMAs",
     "sepconv:K:h..:v..[:lsb]": "rank-one KxK float correlation v (x) h (separable MFMA path)",
     "...@border": "per-stencil border: reflect101 | replicate | constant | skip",
+    # two-image ops: X the current image, H the held one (same channels), every rule per byte
+    "hold (save)": "the current image also becomes the held image (moves no pixels; a second hold replaces the first)",
+    "swap": "current and held exchange roles (moves no pixels)",
+    "add": "min(255, X + H)",
+    "sub": "max(0, H - X)  (held minus current)",
+    "rsub": "max(0, X - H)",
+    "absdiff": "|X - H|",
+    "min / max": "byte minimum / maximum of X and H",
+    "lincomb:a:b[:c]": "sat((qa X + qb H + qc + 2048) >> 12), q = nearbyint(4096 .): |a|, |b| < 8, |c| <= 2048",
+    "blend:t": "lincomb with qa = nearbyint(4096 t), qb = 4096 - qa, 0 <= t <= 1 (equal images are fixed points)",
+    "above[:d]": "H - X + d > 0 ? 255 : 0, integer d in [-255, 255]",
+    "gradient3 / gradient5": "morphological gradient: hold,dilateK,swap,erodeK,sub",
+    "tophat3 / tophat5": "x - open(x): hold,openK,sub",
+    "blackhat3 / blackhat5": "close(x) - x: hold,closeK,rsub",
+    "unsharp[:S[:K]]": "x + S (x - gaussianK(x)): hold,gaussianK,lincomb:-S:1+S; S in (0, 7) default 1, K in 3|5|7 "
+                       "default 5; flat regions stay",
+    "threshold:adaptive:K[:C]": "x > boxK(x) - C ? 255 : 0 (OpenCV ADAPTIVE_THRESH_MEAN_C): hold,boxK,above:C; K in 3|5",
 }
 
 _cache_lock = threading.Lock()
@@ -91,8 +108,8 @@ def _shape(x):
     raise ValueError(f"image must be HxW or HxWx3 uint8, got shape {tuple(x.shape)}")
 
 
-def _engine(W, H, Cc, chain, border, fuse, device_index, halo=True):
-    key = (W, H, Cc, chain, border, fuse, device_index, halo)
+def _engine(W, H, Cc, chain, border, fuse, device_index, halo=True, held=False):
+    key = (W, H, Cc, chain, border, fuse, device_index, halo, held)
     with _cache_lock:
         eng = _engines.get(key)
         if eng is not None:
@@ -104,6 +121,7 @@ def _engine(W, H, Cc, chain, border, fuse, device_index, halo=True):
         cfg.border = C.parse_border(border)
         cfg.fuse = bool(fuse)
         cfg.halo = bool(halo)
+        cfg.held_input = bool(held)
         cfg.device = int(device_index)
         cfg.backend = C.Backend.device
         eng = C.Engine(cfg)
@@ -349,6 +367,103 @@ def otsu_level(x) -> int:
     return int(C.otsu_level(histogram(x)))
 
 
+# ---- two-image ops -------------------------------------------------------------
+def unsharp_mask(x, amount: float = 1.0, ksize: int = 5, border: str = "reflect101"):
+    """x + amount * (x - gaussian_ksize(x)) in Q12 fixed point (`FILTERS['unsharp[:S[:K]]']`)."""
+    return apply(x, f"unsharp:{float(amount)!r}:{int(ksize)}", border)
+
+
+def morph_gradient(x, k: int = 3, border: str = "reflect101"):
+    """dilate_k(x) - erode_k(x)."""
+    return apply(x, f"gradient{int(k)}", border)
+
+
+def top_hat(x, k: int = 3, border: str = "reflect101"):
+    """x - open_k(x)."""
+    return apply(x, f"tophat{int(k)}", border)
+
+
+def black_hat(x, k: int = 3, border: str = "reflect101"):
+    """close_k(x) - x."""
+    return apply(x, f"blackhat{int(k)}", border)
+
+
+def adaptive_threshold(x, ksize: int = 3, c: int = 0, border: str = "reflect101"):
+    """x > box_ksize(x) - c ? 255 : 0 (OpenCV's ADAPTIVE_THRESH_MEAN_C on box's own rounding)."""
+    return apply(x, f"threshold:adaptive:{int(ksize)}:{int(c)}", border)
+
+
+def combine(x, y, op: str, border: str = "reflect101"):
+    """Run the chain `op` on x with y as the held image: a combine token (add, sub, rsub, absdiff, min, max,
+    lincomb:a:b[:c], blend:t, above[:d]) or any chain that reads the held image.  x and y have the same
+    shape; CUDA tensors run on the k_combine HIP kernel, numpy arrays / CPU tensors on the host executor."""
+    if tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f"combine needs two images of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.ndim == 4:
+        outs = [combine(x[b], y[b], op, border) for b in range(x.shape[0])]
+        if _is_tensor(x):
+            return torch.stack(outs) if outs else x.new_empty(tuple(x.shape))
+        return np.stack(outs) if outs else np.empty(tuple(x.shape), np.uint8)
+    if _is_tensor(x) and x.is_cuda:
+        if not (_is_tensor(y) and y.is_cuda and y.device == x.device):
+            raise ValueError("combine needs both tensors on the same GPU")
+        if x.dtype != torch.uint8 or y.dtype != torch.uint8:
+            raise TypeError("image tensors must be uint8")
+        xc, yc = x.contiguous(), y.contiguous()
+        W, H, Cc = _shape(xc)
+        eng = _engine(W, H, Cc, op, border, True, xc.device.index, held=True)
+        stream = torch.cuda.current_stream(xc.device).cuda_stream
+        cout = eng.out_channels
+        out = torch.empty((H, W) if cout == 1 else (H, W, cout), dtype=torch.uint8, device=xc.device)
+        with eng._lock:
+            if eng._stream != stream:
+                eng.use_external_stream(stream)
+                eng._stream = stream
+            eng.load_packed_ptr(xc.data_ptr(), True)
+            eng.load_held_packed_ptr(yc.data_ptr(), True)
+            eng.run(1)
+            eng.store_packed_ptr(out.data_ptr(), True)
+        xc.record_stream(torch.cuda.current_stream(xc.device))
+        yc.record_stream(torch.cuda.current_stream(xc.device))
+        return out
+    was_tensor = _is_tensor(x)
+    ax = x.numpy() if was_tensor else np.asarray(x)
+    ay = y.numpy() if _is_tensor(y) else np.asarray(y)
+    if ax.dtype != np.uint8 or ay.dtype != np.uint8:
+        raise TypeError("images must be uint8")
+    if ax.ndim == 3 and ax.shape[2] == 1:
+        ax, ay = ax[:, :, 0], ay[:, :, 0]
+    out = C.cpu_apply(np.ascontiguousarray(ax), op, border, True, 0, np.ascontiguousarray(ay))
+    return torch.from_numpy(out) if was_tensor else out
+
+
+def absdiff(x, y):
+    return combine(x, y, "absdiff")
+
+
+def add(x, y):
+    """min(255, x + y)."""
+    return combine(x, y, "add")
+
+
+def subtract(x, y):
+    """max(0, x - y)."""
+    return combine(x, y, "rsub")
+
+
+def blend(x, y, t: float):
+    """t x + (1 - t) y in Q12 fixed point, 0 <= t <= 1."""
+    return combine(x, y, f"blend:{float(t)!r}")
+
+
+def minimum(x, y):
+    return combine(x, y, "min")
+
+
+def maximum(x, y):
+    return combine(x, y, "max")
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -360,4 +475,6 @@ __all__ = [
     "median", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
     "color_matrix", "sepia", "saturation", "swap_rb", "rgb_to_ycbcr", "ycbcr_to_rgb",
     "histogram", "equalize", "autocontrast", "threshold_otsu", "otsu_level",
+    "unsharp_mask", "morph_gradient", "top_hat", "black_hat", "adaptive_threshold",
+    "combine", "absdiff", "add", "subtract", "blend", "minimum", "maximum",
 ]

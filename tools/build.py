@@ -59,6 +59,7 @@ CORE_SOURCES = [
     "hip/blur_sep.hip",
     "hip/jpeg_dev.hip",
     "hip/histogram.hip",
+    "hip/combine.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
