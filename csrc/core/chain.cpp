@@ -332,8 +332,17 @@ Plan compile_chain(const std::vector<Op>& ops, int cin, Border default_border, b
       std::string pro = prog_desc(pending);
       // rank filters (median / erode / dilate) are Direct passes: same halo,
       // margin and launch contracts, their own kernel family (k_rank)
-      p.desc = std::string(si.rank != Rank::None ? "rank " : si.separable ? "separable " : "direct ") + si.name +
-               (pro.empty() ? "" : " prologue[" + pro + "]") + " " + std::to_string(p.cin) +
+      // bilateral filters too (k_bilateral); the pass carries the range table, and S shows in its name
+      p.bilateral = si.bilateral;
+      p.sigma = op.sigma;
+      p.range = op.range;
+      std::string name = si.name;
+      if (si.bilateral) name = op.text.substr(0, op.text.find('@'));
+      p.desc = std::string(si.bilateral            ? "bilateral "
+                           : si.rank != Rank::None ? "rank "
+                           : si.separable          ? "separable "
+                                                   : "direct ") +
+               name + (pro.empty() ? "" : " prologue[" + pro + "]") + " " + std::to_string(p.cin) +
                "->" + std::to_string(p.cout) + "ch border=" + border_name(p.border);
     }
     take_slots(p);

@@ -266,11 +266,35 @@ void rank_row(Rank rank, const uint8_t* const* rows, int C, int E, int EW, uint8
   std::memcpy(o, wire[SN::kOut], (size_t)E);
 }
 
+// One output row (E bytes) of a bilateral filter (filters.h) from the K extended
+// ring rows in window order: per tap a table lookup and two integer
+// accumulations, then the rounded quotient.  D and N hold E sums each.
+void bilateral_row(const StencilInfo& si, const uint8_t* range, const uint8_t* const* rows, int K, int C, int E,
+                   uint32_t* D, uint32_t* N, uint8_t* o) {
+  const int R = K / 2;
+  const uint8_t* cen = rows[R] + (size_t)R * C;
+  std::fill(D, D + E, 0u);
+  std::fill(N, N + E, 0u);
+  for (int dy = 0; dy < K; ++dy)
+    for (int dx = 0; dx < K; ++dx) {
+      const uint8_t* s = rows[dy] + (size_t)dx * C;
+      const uint32_t ws = (uint32_t)si.w[(size_t)dy * K + dx];
+      for (int i = 0; i < E; ++i) {
+        const int d = (int)s[i] - (int)cen[i];
+        const uint32_t w = ws * range[d < 0 ? -d : d];
+        D[i] += w;
+        N[i] += w * s[i];
+      }
+    }
+  for (int i = 0; i < E; ++i) o[i] = bilateral_finish(N[i], D[i]);
+}
+
 void stencil_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out, int W, RowGeom g, int ya, int yb) {
   const StencilInfo& si = stencil_info(p.sid);
   const int K = p.K, R = p.R, C = p.cmid;
   const int E = W * C, EW = (W + 2 * R) * C;
   const bool rank = si.rank != Rank::None;
+  std::vector<uint32_t> bsum(si.bilateral ? (size_t)2 * E : 0);
   STRIPE_CHECK(!rank || K == 3 || K == 5, "rank filters come in sizes 3 and 5");
   std::vector<uint8_t> rwork(rank ? (size_t)K * EW + (size_t)K * K * E : 0);
   std::vector<int> wy;
@@ -308,6 +332,11 @@ void stencil_rows(const Pass& p, const ProgTables& pt, ConstView in, MutView out
       for (int dy = 0; dy < K; ++dy) rows[dy] = slot(y + dy - R);
       if (K == 3) rank_row<3>(si.rank, rows, C, E, EW, rwork.data(), o);
       else rank_row<5>(si.rank, rows, C, E, EW, rwork.data(), o);
+    } else if (si.bilateral) {
+      const uint8_t* rows[5];
+      STRIPE_CHECK(K <= 5, "bilateral filters come in sizes 3 and 5");
+      for (int dy = 0; dy < K; ++dy) rows[dy] = slot(y + dy - R);
+      bilateral_row(si, p.range.data(), rows, K, C, E, bsum.data(), bsum.data() + E, o);
     } else {
       std::fill(acc.begin(), acc.end(), 0);
       int32_t* a = acc.data();

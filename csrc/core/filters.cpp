@@ -2,6 +2,7 @@
 #include "stripe/filters.h"
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -66,6 +67,15 @@ StencilInfo make_rank(StencilId id, const char* name) {
   return s;
 }
 
+template <class F>
+StencilInfo make_bilateral(StencilId id, const char* name) {
+  static_assert(!F::SEP && !F::SOBEL && F::DIV == 1 && F::BILATERAL != 0, "bilateral filter definition");
+  StencilInfo s = make_info<F>(id, name);  // w: the spatial weights
+  for (int i = 0; i < F::K; ++i) s.w1.push_back(F::g(i));
+  s.bilateral = true;
+  return s;
+}
+
 const std::vector<StencilInfo>& table() {
   static const std::vector<StencilInfo> t = [] {
     std::vector<StencilInfo> v((size_t)StencilId::kCount);
@@ -86,6 +96,8 @@ const std::vector<StencilInfo>& table() {
     v[(int)StencilId::Erode5] = make_rank<sdef::Erode5>(StencilId::Erode5, "erode5");
     v[(int)StencilId::Dilate3] = make_rank<sdef::Dilate3>(StencilId::Dilate3, "dilate3");
     v[(int)StencilId::Dilate5] = make_rank<sdef::Dilate5>(StencilId::Dilate5, "dilate5");
+    v[(int)StencilId::Bilateral3] = make_bilateral<sdef::Bilateral3>(StencilId::Bilateral3, "bilateral3");
+    v[(int)StencilId::Bilateral5] = make_bilateral<sdef::Bilateral5>(StencilId::Bilateral5, "bilateral5");
     return v;
   }();
   return t;
@@ -143,7 +155,27 @@ std::string q12_text(int q) {
   return os.str();
 }
 
+// The shortest decimal that strtod reads back as exactly v: plain digits where
+// a few decimals do ("20", "3.5"), 17 significant digits otherwise.
+std::string shortest_text(double v) {
+  char buf[64];
+  for (int dec = 0; dec <= 17; ++dec) {
+    std::snprintf(buf, sizeof buf, "%.*f", dec, v);
+    if (std::strtod(buf, nullptr) == v) return buf;
+  }
+  std::snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
+}
+
 }  // namespace
+
+std::array<uint8_t, 256> bilateral_range_table(double S) {
+  STRIPE_CHECK(S > 0.0, "bilateral range sigma must be positive");
+  std::array<uint8_t, 256> r{};
+  for (int d = 0; d < 256; ++d)
+    r[(size_t)d] = (uint8_t)std::nearbyint(255.0 * std::exp(-(double)(d * d) / (2.0 * S * S)));
+  return r;
+}
 
 const char* combine_name(CombineKind k) {
   static const char* names[] = {"add", "sub", "rsub", "absdiff", "min", "max", "lincomb", "above"};
@@ -171,6 +203,8 @@ bool stencil_from_name(const std::string& name, StencilId* out) {
       {"erode3", StencilId::Erode3},     {"erode5", StencilId::Erode5},
       {"dilate", StencilId::Dilate3},    {"dilate3", StencilId::Dilate3},
       {"dilate5", StencilId::Dilate5},
+      {"bilateral", StencilId::Bilateral5}, {"bilateral3", StencilId::Bilateral3},
+      {"bilateral5", StencilId::Bilateral5},
   };
   auto it = alias.find(name);
   if (it == alias.end()) return false;
@@ -545,6 +579,19 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
         set_color_matrix(op, m, b, tok);
       }
       op.text = inv ? "ycbcr:inv" : "ycbcr";
+    } else if (name.compare(0, 9, "bilateral") == 0) {
+      // bilateral3[:S] / bilateral5[:S] / bilateral[:S]  (filters.h); S is the range sigma
+      const std::string sz = name.substr(9);
+      STRIPE_CHECK(sz.empty() || sz == "3" || sz == "5",
+                   "'" << name << "': bilateral takes a window size of 3 or 5 (bilateral3, bilateral5)");
+      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': bilateral syntax: bilateral3[:S], bilateral5[:S]");
+      const double S = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 25.0;
+      STRIPE_CHECK(S > 0.0 && S <= 10000.0, "'" << tok << "': the range sigma must be in (0, 10000]");
+      op.kind = OpKind::Stencil;
+      op.sid = sz == "3" ? StencilId::Bilateral3 : StencilId::Bilateral5;
+      op.sigma = S;
+      op.range = bilateral_range_table(S);
+      op.text = std::string(stencil_info(op.sid).name) + ":" + shortest_text(S);
     } else if (stencil_from_name(name, &sid)) {
       op.kind = OpKind::Stencil;
       op.sid = sid;
@@ -553,7 +600,7 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
       fail("unknown filter '" + name +
            "' (gray[:ref|bt601], contrast:F[:cv], invert, brightness:D, threshold:T, expand, "
            "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
-           "erode3/5, dilate3/5, open3/5, close3/5, blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
+           "erode3/5, dilate3/5, open3/5, close3/5, bilateral3/5[:S], blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
            "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv], "
            "equalize, autocontrast[:P], threshold:otsu, "
            "hold, swap, add, sub, rsub, absdiff, min, max, lincomb:a:b[:c], blend:t, above[:d], "

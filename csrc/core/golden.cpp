@@ -187,6 +187,20 @@ void golden_pass(const Pass& p, ConstView in, MutView out, int W, RowGeom g, int
             std::nth_element(win, win + n / 2, win + n);
             v = win[n / 2];
           }
+        } else if (si.bilateral) {
+          // bilateral: spatial weight x range weight of |p - centre| (filters.h)
+          const int cv = rc.at(y, x)[c];
+          uint32_t D = 0, N = 0;
+          for (int dy = 0; dy < K; ++dy) {
+            const uint8_t* r = rc.at(y + dy - R, x - R) + c;
+            for (int dx = 0; dx < K; ++dx) {
+              const int pv = r[(size_t)dx * C];
+              const uint32_t w = (uint32_t)si.w[(size_t)dy * K + dx] * p.range[(size_t)std::abs(pv - cv)];
+              D += w;
+              N += w * (uint32_t)pv;
+            }
+          }
+          v = bilateral_finish(N, D);
         } else {
           int s = 0, s2 = 0;
           for (int dy = 0; dy < K; ++dy) {

@@ -171,6 +171,7 @@ enum class Family {
   SobelRp,        // k_sobel_rp
   Direct,         // k_direct
   Rank,           // k_rank
+  Bilateral,      // k_bilateral
   ConvSmall,      // k_conv_small
   PointwiseChan,  // k_pointwise (channel-changing)
   PointwiseFlat,  // k_pointwise_flat
@@ -206,7 +207,8 @@ inline int stencil_cap(bool nt, int wgs, int family_default) {
   if (wgs >= 0) return wgs;
   return nt ? family_default : 0;
 }
-// Family default of stencil_cap (the gray-prologue direct / rank kernels gain nothing).
+// Family default of stencil_cap (the gray-prologue direct / rank kernels gain nothing;
+// the bilateral family starts from the rank family's values).
 constexpr int stencil_cap_default(Family f, bool gray_prologue) {
   return f == Family::Sep || f == Family::SobelRp ? dev::kNtWgsSep : gray_prologue ? 0 : dev::kNtWgsDirect;
 }
@@ -230,7 +232,8 @@ inline StreamPolicy stream_policy(const PolicyIn& in) {
     case Family::Sep:
     case Family::SobelRp:
     case Family::Direct:
-    case Family::Rank: {
+    case Family::Rank:
+    case Family::Bilateral: {
       // Output stores bypass the caches (nt) when the pass streams more than the
       // Infinity Cache holds: then the next pass cannot hit in it anyway (16K RGB
       // frame: gaussian5 0.322 -> 0.319 ms, reference chain 0.239 -> 0.227 ms).  A

@@ -160,6 +160,8 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
   dev::KArgs a{};
   const auto [n0, n1, tiles] = dev::fill_tile_args(p, L, a, &kTileView);
   a.luts = pc.luts;
+  STRIPE_CHECK(!p.bilateral || pc.luts_bytes >= (size_t)(kLutBytes + kRangeBytes),
+               "bilateral pass without its range table in the constant block");
   a.out_px = p.out_margin_px;
   a.out_border = (int)p.out_margin_border;
   a.has_pre = 0;

@@ -3,7 +3,8 @@
 // compile in parallel) and stencil.hip: k_sep (separable filters, sep_task),
 // k_sobel_rp (gray sobel on row pairs), k_direct (K x K taps) and ring_task,
 // the register-ring row walk of k_direct as a device function that takes the
-// row operation; k_rank (rank_kernels.h) is a wrapper of it.
+// row operation; k_rank (rank_kernels.h) and k_bilateral (bilateral_kernels.h)
+// are wrappers of it.
 #pragma once
 
 // Integer stencil passes with fused pointwise prologue/epilogue (gfx950).
@@ -1195,6 +1196,19 @@ struct RankTag<F, std::void_t<decltype(F::RANK)>> {
 template <int C, class F, int PRO, bool EXP>
 void launch_rank(bool skip, const KArgs& a, const BandLaunch& B);
 
+// Bilateral filters (sdef::BilateralDef) likewise: k_bilateral and
+// launch_bilateral are defined in bilateral_kernels.h (stencil_inst_f.hip).
+template <class F, class = void>
+struct BilateralTag {
+  static constexpr int value = 0;
+};
+template <class F>
+struct BilateralTag<F, std::void_t<decltype(F::BILATERAL)>> {
+  static constexpr int value = F::BILATERAL;
+};
+template <int C, class F, int PRO, bool EXP>
+void launch_bilateral(bool skip, const KArgs& a, const BandLaunch& B);
+
 // B.order counts on the plain path only (sep_order_supported).
 template <int C, class F, int PRO, bool EXP = false>
 void launch_one(bool skip, const KArgs& a, BandLaunch B) {
@@ -1233,6 +1247,8 @@ void launch_one(bool skip, const KArgs& a, BandLaunch B) {
   }
   if constexpr (RankTag<F>::value != 0) {
     launch_rank<C, F, PRO, EXP>(skip, a, B);
+  } else if constexpr (BilateralTag<F>::value != 0) {
+    launch_bilateral<C, F, PRO, EXP>(skip, a, B);
   } else if constexpr (F::SEP) {
     const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP>, k_sep<C, F, PRO, false, kNtAux, EXP>,
                       k_sep<C, F, PRO, true, 0, EXP>, k_sep<C, F, PRO, true, kNtAux, EXP>};
@@ -1275,7 +1291,7 @@ void launch_filter(const Pass& p, const KArgs& a, const BandLaunch& B) {
 #define STRIPE_INSTANTIATE_LAUNCH_FILTER(F) template STRIPE_LAUNCH_FILTER_SIG(F);
 #define STRIPE_STENCIL_FILTERS(X) \
   X(Emboss3) X(Emboss5) X(Sharpen) X(Laplace) X(Sobel) X(SobelL2) X(Gaussian3) X(Gaussian5) X(Gaussian7) X(Box3) \
-  X(Box5) X(Median3) X(Median5) X(Erode3) X(Erode5) X(Dilate3) X(Dilate5)
+  X(Box5) X(Median3) X(Median5) X(Erode3) X(Erode5) X(Dilate3) X(Dilate5) X(Bilateral3) X(Bilateral5)
 
 }  // namespace dev
 }  // namespace stripe

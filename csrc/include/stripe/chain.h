@@ -80,6 +80,10 @@ struct Pass {
   CombineKind comb = CombineKind::Add;
   int cq[3] = {0, 0, 0};
   int cd = 0;
+  // bilateral stencil: the range sigma and its table (Op::sigma, Op::range)
+  bool bilateral = false;
+  double sigma = 0.0;
+  std::array<uint8_t, 256> range{};
   // slot actions that precede the pass, in order: 'h' hold (the current image
   // also becomes the held image), 's' swap (current and held exchange roles)
   std::string slots;

@@ -378,7 +378,7 @@ class Engine {
   Pass prepare_stat(const Pass& p, const uint8_t* in, int pi);
   Histogram stripe_histogram(const uint8_t* org, int C);
   Histogram reduce_histogram(const Histogram& local, bool idle_ranks_receive);
-  void fill_lut_block(const Pass& p, uint8_t* l) const;  // [pre | post | epi]
+  void fill_lut_block(const Pass& p, uint8_t* l) const;  // [pre | post | epi] (a bilateral pass's range block follows it)
   Buffer hist_dev_;          // device engine: the 256 x 3 u32 table k_hist adds to
   Buffer hist_stage_;        // all-reduce staging where the communicator's buffers live
   PinnedBuffer hist_host_;   // device engine: counts, LUT block and all-reduce staging on the host

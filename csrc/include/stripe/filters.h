@@ -73,6 +73,23 @@
 //                 defaults to 5; flat regions are fixed points
 //   threshold:adaptive:K[:C]  hold,boxK,above:C, K in {3,5}, C defaults to 0:
 //                 OpenCV's ADAPTIVE_THRESH_MEAN_C on boxK's own rounding
+//
+// Bilateral filters (bilateral3[:S], bilateral5[:S], bilateral[:S] = bilateral5):
+// an edge-preserving smoother, per channel, over the K x K window of the
+// border-extended, prologue-applied image.  S is the range sigma in grey
+// levels, 0 < S <= 10000, default 25.  With c the centre pixel and p(dy,dx) the
+// window pixels:
+//   ws(dy,dx) = g[dy] g[dx]             g: the binomial taps of gaussianK
+//   r[d]      = rint(255 exp(-d^2 / (2 S^2)))   d = 0..255, computed once by
+//               the parser in double (bilateral_range_table); no other layer
+//               calls exp
+//   w = ws r[|p - c|],  D = sum w,  N = sum w p
+//   out = (N + (D >> 1)) / D            floor division (bilateral_finish)
+// D >= ws(centre) 255 > 0 and D <= 256 * 255 = 65280 (u16); every w <= 36 * 255;
+// N + (D >> 1) < 2^24; out <= 255 without a clamp.  Flat images are fixed
+// points; for S >= 4096 every r[d] is 255 and the rule is gaussianK's own
+// (sum + DIV/2) / DIV.  On RGB it is per channel, not OpenCV's joint colour
+// distance.
 #pragma once
 
 #include <array>
@@ -140,6 +157,8 @@ enum class StencilId : int {
   Erode5,
   Dilate3,
   Dilate5,
+  Bilateral3,
+  Bilateral5,
   kCount
 };
 
@@ -160,6 +179,9 @@ struct StencilInfo {
   std::vector<int> w;    // K*K row-major [dy][dx] (correlation, like filter2D)
   std::vector<int> w1;   // separable 1-D taps
   Rank rank = Rank::None;  // rank filter: w / w1 empty, div 1
+  // bilateral filter: w = the spatial weights ws, w1 = g, div 1; the range
+  // table travels with the op and the pass (Op::range, Pass::range)
+  bool bilateral = false;
 };
 
 const StencilInfo& stencil_info(StencilId id);
@@ -176,6 +198,8 @@ struct Op {
   int cm[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // colour matrix: q row-major, then qb (kColorShift)
   CombineKind comb = CombineKind::Add;  // OpKind::Combine
   int cq[3] = {0, 0, 0};                // lincomb / blend: qa, qb, qc (kColorShift); above: d in ival
+  double sigma = 0.0;                   // bilateral: the range sigma S
+  std::array<uint8_t, 256> range{};     // bilateral: r[d] (bilateral_range_table)
   int K = 0;                  // conv window
   std::vector<float> weights; // conv: K*K f32 weights
   std::vector<float> sep_h, sep_v;  // conv: 1-D factors when weights[dy][dx] = sep_v[dy] * sep_h[dx]
@@ -226,6 +250,11 @@ inline uint8_t combine_rule(CombineKind k, const int* cq, int d, uint8_t x, uint
   return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 inline uint8_t combine_u8(const Op& op, uint8_t x, uint8_t h) { return combine_rule(op.comb, op.cq, op.ival, x, h); }
+
+// Bilateral filter (rule at the top of this file).  The range table of sigma S
+// (the parser's one call), and the rounded quotient of a pixel's sums.
+std::array<uint8_t, 256> bilateral_range_table(double S);
+inline uint8_t bilateral_finish(uint32_t N, uint32_t D) { return (uint8_t)((N + (D >> 1)) / D); }
 
 // Statistic ops (rules at the top of this file): the table of `op`
 // (OpKind::Stat) for an image with histogram `h` (channels pooled), and Otsu's

@@ -27,10 +27,14 @@ namespace stripe {
 // Device-resident per-pass constants, built once by the engine.
 // Per-pass LUT block: [pre 256 | post 256 | epi 256] (the gray:ref terms are
 // computed by multiply-shift in the kernels).
+// A bilateral pass appends its range table: [pre | post | epi | range], 1024
+// bytes.  Run-time tables (statistic ops) re-upload the first kLutBytes only.
 constexpr int kLutBytes = 768;
+constexpr int kRangeBytes = 256;
 
 struct PassConsts {
   uint8_t* luts = nullptr;   // kLutBytes, layout above
+  size_t luts_bytes = kLutBytes;  // kLutBytes + kRangeBytes for a bilateral pass
   void* conv = nullptr;      // conv pass: packed MFMA operand tables
   size_t conv_bytes = 0;
   int conv_mode = 0;         // general conv: 0 f16 hi+lo row pairs, 1 i8 weight digits (k_conv_i8)

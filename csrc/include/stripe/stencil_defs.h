@@ -155,5 +155,20 @@ struct Erode5 : RankDef<5, kRankMin> {};
 struct Dilate3 : RankDef<3, kRankMax> {};
 struct Dilate5 : RankDef<5, kRankMax> {};
 
+// Bilateral filters (filters.h): the spatial weights are g (x) g with the
+// binomial taps of gaussianK; the range table is run-time data of the pass.  A
+// compile-time tag selects the kernel family, as RANK does.
+template <class G>
+struct BilateralDef {
+  static constexpr bool BINOM = false;
+  static constexpr int K = G::K, R = G::R, DIV = 1;
+  static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int BILATERAL = 1;
+  STRIPE_HD static constexpr int g(int i) { return G::g(i); }
+  STRIPE_HD static constexpr int w(int dy, int dx) { return G::g(dy) * G::g(dx); }
+};
+struct Bilateral3 : BilateralDef<Gaussian3> {};
+struct Bilateral5 : BilateralDef<Gaussian5> {};
+
 }  // namespace sdef
 }  // namespace stripe

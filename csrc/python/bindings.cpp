@@ -194,6 +194,7 @@ PYBIND11_MODULE(_C, m) {
     d["separable"] = s.separable;
     d["sobel"] = s.sobel;
     d["rank"] = rank_name(s.rank);  // "none" | "min" | "max" | "median" (rank filters: w empty)
+    d["bilateral"] = s.bilateral;   // w: the spatial weights; the range table: bilateral_table
     return d;
   });
   m.def("color_matrix", [](const std::string& token) {
@@ -208,6 +209,13 @@ PYBIND11_MODULE(_C, m) {
     d["shift"] = kColorShift;
     return d;
   }, "Q12 coefficients of a colour matrix token: out_c = sat((sum_k q[c][k] p_k + b[c] + 2048) >> 12)");
+  m.def("bilateral_table", [](const std::string& token) {
+    // the range table of one bilateral token, for the tests
+    auto ops = parse_chain(token);
+    STRIPE_CHECK(ops.size() == 1 && ops[0].kind == OpKind::Stencil && stencil_info(ops[0].sid).bilateral,
+                 "bilateral_table needs one bilateral token");
+    return std::vector<int>(ops[0].range.begin(), ops[0].range.end());
+  }, "r[d] = rint(255 exp(-d^2 / (2 S^2))), d = 0..255, of a bilateral token (filters.h)");
   m.def("rank_network", [](int K) {
     // the median networks of rank_net.h as (i, j, mode) steps, for the tests
     STRIPE_CHECK(K == 3 || K == 5, "rank networks exist for K = 3 and 5");
@@ -274,6 +282,8 @@ PYBIND11_MODULE(_C, m) {
       q["combine"] = ps.kind == PassKind::Combine ? std::string(combine_name(ps.comb)) : std::string();
       q["post_lut"] = ps.kind == PassKind::Combine && ps.pro.has_post;
       q["fill_in"] = ps.fill_in;
+      q["bilateral"] = ps.bilateral;
+      q["sigma"] = ps.bilateral ? ps.sigma : 0.0;  // the range sigma S
       passes.append(q);
     }
     d["passes"] = passes;
@@ -289,6 +299,7 @@ PYBIND11_MODULE(_C, m) {
     static const std::pair<const char*, policy::Family> names[] = {
         {"sep", policy::Family::Sep},           {"sobel_rp", policy::Family::SobelRp},
         {"direct", policy::Family::Direct},     {"rank", policy::Family::Rank},
+        {"bilateral", policy::Family::Bilateral},
         {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
         {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine}};
@@ -317,7 +328,7 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("family"), py::arg("cin") = 3, py::arg("cout") = 3, py::arg("cmid") = 3, py::arg("W") = 0,
      py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
      py::arg("lut_stage") = false,
-     "the launch decision of a kernel family: sep | sobel_rp | direct | rank | conv_small | pointwise | "
+     "the launch decision of a kernel family: sep | sobel_rp | direct | rank | bilateral | conv_small | pointwise | "
      "pointwise_flat | colormix | blur | combine");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));

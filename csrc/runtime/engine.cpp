@@ -151,16 +151,20 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
     const Pass& p = plan_.passes[i];
     // (a statistic pass: the static tables, i.e. an identity statistic, until
     // prepare_stat uploads the table of the pass's input)
-    std::vector<uint8_t> l(kLutBytes);
+    // (a bilateral pass: its range table as a fourth block, uploaded here once)
+    const size_t lbytes = kLutBytes + (p.bilateral ? kRangeBytes : 0);
+    std::vector<uint8_t> l(lbytes);
     fill_lut_block(p, l.data());
-    prt_[i].luts = Buffer(kLutBytes, device());
+    if (p.bilateral) std::memcpy(l.data() + kLutBytes, p.range.data(), kRangeBytes);
+    prt_[i].luts = Buffer(lbytes, device());
     if (device()) {
-      HIP_CHECK(hipMemcpy(prt_[i].luts.data(), l.data(), kLutBytes, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(prt_[i].luts.data(), l.data(), lbytes, hipMemcpyHostToDevice));
       if (p.kind == PassKind::Conv) prepare_conv_consts(p, &prt_[i].pc, s_compute_);
     } else {
-      std::memcpy(prt_[i].luts.data(), l.data(), kLutBytes);
+      std::memcpy(prt_[i].luts.data(), l.data(), lbytes);
     }
     prt_[i].pc.luts = prt_[i].luts.data();
+    prt_[i].pc.luts_bytes = lbytes;
   }
   cur_c_ = cfg_.C;
   if (device()) HIP_CHECK(hipDeviceSynchronize());

@@ -67,6 +67,10 @@ FILTERS = {
     "dilate3 / dilate5 (dilate)": "maximum of the KxK window",
     "open3 / open5": "erodeK,dilateK (an @border suffix applies to both)",
     "close3 / close5": "dilateK,erodeK",
+    "bilateral3[:S] / bilateral5[:S] (bilateral)": "edge-preserving smoothing, per channel: binomial taps times "
+                                                   "r[|p - centre|], r[d] = rint(255 exp(-d^2 / (2 S^2))), "
+                                                   "out = (sum w p + D/2) / D exactly; S = range sigma in grey "
+                                                   "levels, 0 < S <= 10000, default 25 (S >= 4096: gaussianK)",
     "blur:K[:sigma][:lsb]": "KxK float Gaussian (separable MFMA path), K <= 33; :lsb = every output within 1 LSB, "
                             "2.5x fewer MFMAs",
     "conv:K:w0;w1;...[:lsb]": "generic KxK float correlation (MFMA path); :lsb = within 1 LSB, 2/3 of the MFMAs",
@@ -233,6 +237,13 @@ def emboss(x, size: int = 3, border: str = "reflect101"):
 
 def median(x, k: int = 3, border: str = "reflect101"):
     return apply(x, f"median{int(k)}", border)
+
+
+def bilateral(x, sigma: float = 25.0, ksize: int = 5, border: str = "reflect101"):
+    """Bilateral filter, per channel: ksize 3 or 5, sigma the range sigma in grey levels."""
+    if int(ksize) not in (3, 5):
+        raise ValueError(f"bilateral window size must be 3 or 5, got {ksize}")
+    return apply(x, f"bilateral{int(ksize)}:{float(sigma)!r}", border)
 
 
 def erode(x, k: int = 3, border: str = "reflect101"):
@@ -472,7 +483,7 @@ def clear_cache() -> None:
 __all__ = [
     "FILTERS", "apply", "reference", "grayscale", "contrast", "invert", "brightness", "threshold",
     "gaussian_blur", "box_blur", "sobel", "sharpen", "laplace", "emboss",
-    "median", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
+    "median", "bilateral", "erode", "dilate", "morph_open", "morph_close", "conv2d", "sep_conv2d", "large_blur", "clear_cache",
     "color_matrix", "sepia", "saturation", "swap_rb", "rgb_to_ycbcr", "ycbcr_to_rgb",
     "histogram", "equalize", "autocontrast", "threshold_otsu", "otsu_level",
     "unsharp_mask", "morph_gradient", "top_hat", "black_hat", "adaptive_threshold",

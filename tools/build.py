@@ -55,6 +55,7 @@ CORE_SOURCES = [
     "hip/stencil_inst_c.hip",
     "hip/stencil_inst_d.hip",
     "hip/stencil_inst_e.hip",
+    "hip/stencil_inst_f.hip",
     "hip/conv.hip",
     "hip/blur_sep.hip",
     "hip/jpeg_dev.hip",
