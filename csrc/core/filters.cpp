@@ -4,8 +4,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <mutex>
+#include <cstring>
+#include <initializer_list>
 
 #include "stripe/stencil_defs.h"
 
@@ -31,75 +31,37 @@ Border parse_border(const std::string& s) {
 
 namespace {
 
+// The catalogue row of definition F (stencil_defs.h): weighted stencils carry
+// w (and w1 when w = w1 (x) w1), rank filters a rank, bilateral filters both
+// the spatial weights and their taps.
 template <class F>
-StencilInfo make_info(StencilId id, const char* name) {
+StencilInfo make_info(StencilId id, std::initializer_list<const char*> names) {
+  static_assert(F::RANK == 0 || (!F::SEP && !F::SOBEL && F::DIV == 1 && F::BILATERAL == 0), "rank filter definition");
+  static_assert(F::BILATERAL == 0 || (!F::SEP && !F::SOBEL && F::DIV == 1 && F::RANK == 0),
+                "bilateral filter definition");
   StencilInfo s;
   s.id = id;
-  s.name = name;
+  s.names = names;
+  s.name = s.names.front();
   s.K = F::K;
   s.separable = F::SEP;
   s.sobel = F::SOBEL;
   if constexpr (F::SOBEL) s.l2 = F::L2;
   s.div = F::DIV;
-  for (int dy = 0; dy < F::K; ++dy)
-    for (int dx = 0; dx < F::K; ++dx) s.w.push_back(F::w(dy, dx));
-  return s;
-}
-
-template <class F>
-StencilInfo make_sep(StencilId id, const char* name) {
-  StencilInfo s = make_info<F>(id, name);
-  for (int i = 0; i < F::K; ++i) s.w1.push_back(F::g(i));
-  return s;
-}
-
-template <class F>
-StencilInfo make_rank(StencilId id, const char* name) {
-  static_assert(!F::SEP && !F::SOBEL && F::DIV == 1 && F::RANK != 0, "rank filter definition");
-  StencilInfo s;
-  s.id = id;
-  s.name = name;
-  s.K = F::K;
-  s.separable = false;
-  s.sobel = false;
-  s.div = 1;
   s.rank = (Rank)F::RANK;
-  return s;
-}
-
-template <class F>
-StencilInfo make_bilateral(StencilId id, const char* name) {
-  static_assert(!F::SEP && !F::SOBEL && F::DIV == 1 && F::BILATERAL != 0, "bilateral filter definition");
-  StencilInfo s = make_info<F>(id, name);  // w: the spatial weights
-  for (int i = 0; i < F::K; ++i) s.w1.push_back(F::g(i));
-  s.bilateral = true;
+  s.bilateral = F::BILATERAL != 0;
+  if constexpr (F::RANK == 0)
+    for (int dy = 0; dy < F::K; ++dy)
+      for (int dx = 0; dx < F::K; ++dx) s.w.push_back(F::w(dy, dx));
+  if constexpr ((F::SEP && !F::SOBEL) || F::BILATERAL != 0)
+    for (int i = 0; i < F::K; ++i) s.w1.push_back(F::g(i));
   return s;
 }
 
 const std::vector<StencilInfo>& table() {
-  static const std::vector<StencilInfo> t = [] {
-    std::vector<StencilInfo> v((size_t)StencilId::kCount);
-    v[(int)StencilId::Emboss3] = make_info<sdef::Emboss3>(StencilId::Emboss3, "emboss3");
-    v[(int)StencilId::Emboss5] = make_info<sdef::Emboss5>(StencilId::Emboss5, "emboss5");
-    v[(int)StencilId::Gaussian3] = make_sep<sdef::Gaussian3>(StencilId::Gaussian3, "gaussian3");
-    v[(int)StencilId::Gaussian5] = make_sep<sdef::Gaussian5>(StencilId::Gaussian5, "gaussian5");
-    v[(int)StencilId::Gaussian7] = make_sep<sdef::Gaussian7>(StencilId::Gaussian7, "gaussian7");
-    v[(int)StencilId::Box3] = make_sep<sdef::Box3>(StencilId::Box3, "box3");
-    v[(int)StencilId::Box5] = make_sep<sdef::Box5>(StencilId::Box5, "box5");
-    v[(int)StencilId::Sharpen] = make_info<sdef::Sharpen>(StencilId::Sharpen, "sharpen");
-    v[(int)StencilId::Laplace] = make_info<sdef::Laplace>(StencilId::Laplace, "laplace");
-    v[(int)StencilId::Sobel] = make_info<sdef::Sobel>(StencilId::Sobel, "sobel");
-    v[(int)StencilId::SobelL2] = make_info<sdef::SobelL2>(StencilId::SobelL2, "sobel_l2");
-    v[(int)StencilId::Median3] = make_rank<sdef::Median3>(StencilId::Median3, "median3");
-    v[(int)StencilId::Median5] = make_rank<sdef::Median5>(StencilId::Median5, "median5");
-    v[(int)StencilId::Erode3] = make_rank<sdef::Erode3>(StencilId::Erode3, "erode3");
-    v[(int)StencilId::Erode5] = make_rank<sdef::Erode5>(StencilId::Erode5, "erode5");
-    v[(int)StencilId::Dilate3] = make_rank<sdef::Dilate3>(StencilId::Dilate3, "dilate3");
-    v[(int)StencilId::Dilate5] = make_rank<sdef::Dilate5>(StencilId::Dilate5, "dilate5");
-    v[(int)StencilId::Bilateral3] = make_bilateral<sdef::Bilateral3>(StencilId::Bilateral3, "bilateral3");
-    v[(int)StencilId::Bilateral5] = make_bilateral<sdef::Bilateral5>(StencilId::Bilateral5, "bilateral5");
-    return v;
-  }();
+#define STRIPE_INFO_ROW(Id, ...) make_info<sdef::Id>(StencilId::Id, {__VA_ARGS__}),
+  static const std::vector<StencilInfo> t = {STRIPE_STENCILS(STRIPE_INFO_ROW)};
+#undef STRIPE_INFO_ROW
   return t;
 }
 
@@ -188,28 +150,13 @@ const StencilInfo& stencil_info(StencilId id) {
 }
 
 bool stencil_from_name(const std::string& name, StencilId* out) {
-  static const std::map<std::string, StencilId> alias = {
-      {"emboss", StencilId::Emboss3},    {"emboss3", StencilId::Emboss3},
-      {"emboss5", StencilId::Emboss5},   {"gaussian", StencilId::Gaussian5},
-      {"gaussian3", StencilId::Gaussian3}, {"gaussian5", StencilId::Gaussian5},
-      {"gaussian7", StencilId::Gaussian7}, {"gauss5", StencilId::Gaussian5},
-      {"box3", StencilId::Box3},         {"box5", StencilId::Box5},
-      {"sharpen", StencilId::Sharpen},   {"laplace", StencilId::Laplace},
-      {"laplacian", StencilId::Laplace}, {"sobel", StencilId::Sobel},
-      {"edge", StencilId::Sobel},        {"sobel_l2", StencilId::SobelL2},
-      {"magnitude", StencilId::SobelL2},
-      {"median", StencilId::Median3},    {"median3", StencilId::Median3},
-      {"median5", StencilId::Median5},   {"erode", StencilId::Erode3},
-      {"erode3", StencilId::Erode3},     {"erode5", StencilId::Erode5},
-      {"dilate", StencilId::Dilate3},    {"dilate3", StencilId::Dilate3},
-      {"dilate5", StencilId::Dilate5},
-      {"bilateral", StencilId::Bilateral5}, {"bilateral3", StencilId::Bilateral3},
-      {"bilateral5", StencilId::Bilateral5},
-  };
-  auto it = alias.find(name);
-  if (it == alias.end()) return false;
-  *out = it->second;
-  return true;
+  for (const StencilInfo& s : table())
+    for (const char* n : s.names)
+      if (name == n) {
+        *out = s.id;
+        return true;
+      }
+  return false;
 }
 
 const char* rank_name(Rank r) {
@@ -249,31 +196,502 @@ std::vector<double> gaussian_1d(int K, double sigma) {
   return g;
 }
 
-static Op make_conv_blur(int K, double sigma, const std::string& text) {
-  STRIPE_CHECK(K >= 3 && K % 2 == 1 && K / 2 <= kMaxRadius,
-               "blur:K needs odd K in [3, " << 2 * kMaxRadius + 1 << "], got " << K);
-  Op op;
-  op.kind = OpKind::Conv;
-  op.K = K;
-  auto g = gaussian_1d(K, sigma);
-  op.weights.resize((size_t)K * K);
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) op.weights[(size_t)i * K + j] = (float)(g[i] * g[j]);
-  op.sep_h.resize((size_t)K);
-  for (int i = 0; i < K; ++i) op.sep_h[(size_t)i] = (float)g[i];
-  op.sep_v = op.sep_h;
-  op.text = text;
-  return op;
+// ---------------------------------------------------------------------------
+// The token table: every spelling a chain token may start with, its row of the
+// catalogue (filter_catalogue) and the function that parses it.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct Entry;
+struct Token {
+  const std::string& text;         // the token without its "@border"; error messages quote it
+  std::vector<std::string> parts;  // text split at ':'; parts[0] is the head name
+  std::string border;              // "@border", canonical, or empty: sugar hands it to its stencils
+  const Entry* entry;              // the table row that matched the head name (nullptr: a plain stencil name)
+  std::string expansion;           // set by sugar and presets: the chain the token stands for
+  const std::string& name() const { return parts[0]; }
+};
+
+// Fills `op` (kind, parameters, canonical text without "@border"), or sets t.expansion.
+using ParseFn = void (*)(Token& t, Op& op);
+
+struct Entry {
+  std::vector<const char*> names;  // head names; none: a catalogue row without a parser of its own
+  bool sized;                      // a family named by its window size: matches names that start with names[0]
+  const char* syntax;              // catalogue row (nullptr: not listed)
+  const char* about;
+  ParseFn parse;
+  const char* chain = nullptr;     // sugar and presets: what the token stands for ('#': window size and @border)
+};
+const std::vector<Entry>& entries();
+
+[[noreturn]] void unknown_filter(const std::string& name) {
+  std::string s = "unknown filter '" + name + "' (";
+  const char* sep = "";
+  for (const Entry& e : entries())
+    if (e.syntax) {
+      s += sep + std::string(e.syntax);
+      sep = ", ";
+    }
+  fail(s + ")");
 }
+
+void no_arguments(const Token& t, const std::string& who) {
+  STRIPE_CHECK(t.parts.size() == 1, "'" << t.text << "': " << who << " takes no arguments");
+}
+
+// The window size of a sized family's token: "3", "5" or, where the bare name
+// is a spelling too, "".  Only the bilateral filters take arguments.
+std::string window_size(const Token& t, bool bare, bool arguments = false) {
+  const std::string f = t.entry->names[0], sz = t.name().substr(f.size());
+  STRIPE_CHECK(sz == "3" || sz == "5" || (sz.empty() && bare),
+               "'" << t.name() << "': " << f << " takes a window size of 3 or 5 (" << f << "3, " << f << "5)");
+  if (!arguments) no_arguments(t, f);
+  return sz;
+}
+
+void set_op(Op& op, OpKind kind, const char* text) {
+  op.kind = kind;
+  op.text = text;
+}
+
 
 // Trailing ":exact" / ":lsb" of a float conv token (removed from parts):
 // 3 = exact (the default), 2 = every output within 1 LSB of the f64 result.
-static int take_precision(std::vector<std::string>& parts) {
+int take_precision(std::vector<std::string>& parts) {
   if (parts.size() < 2) return 3;
   const std::string last = trim(parts.back());
   if (last != "exact" && last != "lsb") return 3;
   parts.pop_back();
   return last == "lsb" ? 2 : 3;
+}
+
+// ---- stencils ----
+void p_stencil(Token& t, Op& op) {  // every name of STRIPE_STENCILS; arguments of a plain stencil are ignored
+  if (!stencil_from_name(t.name(), &op.sid)) unknown_filter(t.name());
+  set_op(op, OpKind::Stencil, stencil_info(op.sid).name);
+}
+
+void p_rank(Token& t, Op& op) {  // median / erode / dilate [3|5]
+  window_size(t, true);
+  p_stencil(t, op);
+}
+
+void p_bilateral(Token& t, Op& op) {  // bilateral[3|5][:S]  (filters.h); S is the range sigma
+  window_size(t, true, true);
+  STRIPE_CHECK(t.parts.size() <= 2, "'" << t.text << "': bilateral syntax: bilateral3[:S], bilateral5[:S]");
+  const double S = t.parts.size() > 1 ? parse_num(trim(t.parts[1]), t.text) : 25.0;
+  STRIPE_CHECK(S > 0.0 && S <= 10000.0, "'" << t.text << "': the range sigma must be in (0, 10000]");
+  p_stencil(t, op);
+  op.sigma = S;
+  op.range = bilateral_range_table(S);
+  op.text += ":" + shortest_text(S);
+}
+
+// ---- sugar: the chain a token stands for; its @border goes to the stencils inside ----
+void p_sized_sugar(Token& t, Op&) {  // open close gradient tophat blackhat [3|5]
+  const std::string k = window_size(t, false) + t.border;
+  for (const char* c = t.entry->chain; *c; ++c) t.expansion += *c == '#' ? k : std::string(1, *c);
+}
+
+void p_unsharp(Token& t, Op&) {
+  // unsharp[:S[:K]]  x + S (x - gaussianK(x)) in Q12: qa = -nearbyint(4096 S) on the blur, 4096 - qa on x
+  STRIPE_CHECK(t.parts.size() <= 3, "'" << t.text << "': unsharp syntax: unsharp[:S[:K]]");
+  const double S = t.parts.size() > 1 ? parse_num(trim(t.parts[1]), t.text) : 1.0;
+  const std::string k = t.parts.size() > 2 ? trim(t.parts[2]) : "5";
+  STRIPE_CHECK(S > 0.0 && S < 7.0, "'" << t.text << "': unsharp amount must be in (0, 7)");
+  STRIPE_CHECK(k == "3" || k == "5" || k == "7", "'" << t.text << "': unsharp blurs with gaussian3, 5 or 7");
+  const int qa = -(int)std::nearbyint(4096.0 * S);
+  STRIPE_CHECK(qa != 0 && 4096 - qa <= 32767, "'" << t.text << "': unsharp amount must be in (0, 7)");
+  t.expansion = "hold,gaussian" + k + t.border + ",lincomb:" + q12_text(qa) + ":" + q12_text(4096 - qa);
+}
+
+// Presets (SURVEY Appendix A "presets"): the bare name only; halo / partition
+// flags of a preset are applied by the callers (CLI / models.PRESETS).
+void p_preset(Token& t, Op&) {
+  if (t.parts.size() != 1 || !t.border.empty()) unknown_filter(t.name());
+  t.expansion = t.entry->chain;
+}
+
+// ---- two-image ops ----
+void p_hold(Token& t, Op& op) { no_arguments(t, t.name()), set_op(op, OpKind::Hold, "hold"); }
+void p_swap(Token& t, Op& op) { no_arguments(t, t.name()), set_op(op, OpKind::Swap, "swap"); }
+
+void p_combine(Token& t, Op& op) {  // add sub rsub absdiff min max: the names of combine_name
+  no_arguments(t, t.name());
+  op.kind = OpKind::Combine;
+  for (int k = 0; k < (int)CombineKind::kCount; ++k)
+    if (t.name() == combine_name((CombineKind)k)) op.comb = (CombineKind)k;
+  op.text = t.name();
+}
+
+void set_lincomb_text(Op& op) {  // lincomb and blend are both spelled canonically as lincomb
+  op.kind = OpKind::Combine;
+  op.comb = CombineKind::LinComb;
+  op.text = "lincomb:" + q12_text(op.cq[0]) + ":" + q12_text(op.cq[1]) +
+            (op.cq[2] != 0 ? ":" + q12_text(op.cq[2]) : std::string());
+}
+
+void p_lincomb(Token& t, Op& op) {  // lincomb:a:b[:c]  (Q12, filters.h)
+  STRIPE_CHECK(t.parts.size() == 3 || t.parts.size() == 4, "'" << t.text << "': lincomb syntax: lincomb:a:b[:c]");
+  for (int i = 0; i < 2; ++i) {
+    const double a = parse_num(trim(t.parts[(size_t)i + 1]), t.text);
+    const double q = std::nearbyint(a * 4096.0);
+    STRIPE_CHECK(std::fabs(q) <= 32767, "'" << t.text << "': coefficient " << a << " out of range (|a| < 8)");
+    op.cq[i] = (int)q;
+  }
+  if (t.parts.size() == 4) {
+    const double c = parse_num(trim(t.parts[3]), t.text);
+    STRIPE_CHECK(std::fabs(c) <= 2048, "'" << t.text << "': offset " << c << " out of range (|c| <= 2048)");
+    op.cq[2] = (int)std::nearbyint(c * 4096.0);
+  }
+  set_lincomb_text(op);
+}
+
+void p_blend(Token& t, Op& op) {  // blend:t
+  STRIPE_CHECK(t.parts.size() == 2, "'" << t.text << "': blend needs a weight, e.g. blend:0.25");
+  const double w = parse_num(trim(t.parts[1]), t.text);
+  STRIPE_CHECK(w >= 0.0 && w <= 1.0, "'" << t.text << "': blend weight must be in [0, 1]");
+  op.cq[0] = (int)std::nearbyint(4096.0 * w);
+  op.cq[1] = 4096 - op.cq[0];
+  set_lincomb_text(op);
+}
+
+void p_above(Token& t, Op& op) {
+  STRIPE_CHECK(t.parts.size() <= 2, "'" << t.text << "': above syntax: above[:d]");
+  const double d = t.parts.size() > 1 ? parse_num(trim(t.parts[1]), t.text) : 0.0;
+  STRIPE_CHECK(d == std::nearbyint(d) && std::fabs(d) <= 255,
+               "'" << t.text << "': above takes an integer offset in [-255, 255]");
+  op.kind = OpKind::Combine;
+  op.comb = CombineKind::Above;
+  op.ival = (int)d;
+  op.text = op.ival != 0 ? "above:" + std::to_string(op.ival) : std::string("above");
+}
+
+// ---- pointwise ----
+void p_gray(Token& t, Op& op) {
+  op.kind = OpKind::Gray;
+  op.gray = GrayMode::BT601;
+  if (t.parts.size() > 1) {
+    if (t.parts[1] == "ref") op.gray = GrayMode::Ref;
+    else if (t.parts[1] == "bt601" || t.parts[1] == "cv") op.gray = GrayMode::BT601;
+    else fail("gray mode must be ref|bt601, got '" + t.parts[1] + "'");
+  }
+  op.text = op.gray == GrayMode::Ref ? "gray:ref" : "gray:bt601";
+}
+
+void p_contrast(Token& t, Op& op) {
+  op.kind = OpKind::Contrast;
+  op.fval = t.parts.size() > 1 ? (float)parse_num(t.parts[1], t.text) : 3.5f;
+  op.round = RoundMode::Trunc;
+  if (t.parts.size() > 2) {
+    if (t.parts[2] == "cv" || t.parts[2] == "round") op.round = RoundMode::Nearest;
+    else if (t.parts[2] == "ref" || t.parts[2] == "trunc") op.round = RoundMode::Trunc;
+    else fail("contrast rounding must be ref|cv, got '" + t.parts[2] + "'");
+  }
+  std::ostringstream os;
+  os << "contrast:" << op.fval << (op.round == RoundMode::Nearest ? ":cv" : "");
+  op.text = os.str();
+}
+
+void p_invert(Token&, Op& op) { set_op(op, OpKind::Invert, "invert"); }
+void p_expand(Token&, Op& op) { set_op(op, OpKind::Expand, "expand"); }
+
+void p_brightness(Token& t, Op& op) {
+  op.kind = OpKind::Brightness;
+  STRIPE_CHECK(t.parts.size() > 1, "brightness needs a delta, e.g. brightness:40");
+  op.ival = (int)parse_num(t.parts[1], t.text);
+  op.text = "brightness:" + std::to_string(op.ival);
+}
+
+// threshold[:T] | threshold:otsu | threshold:adaptive:K[:C]
+void p_threshold(Token& t, Op& op) {
+  const std::string mode = t.parts.size() > 1 ? trim(t.parts[1]) : std::string();
+  if (mode == "adaptive") {  // x > boxK(x) - C
+    STRIPE_CHECK(t.parts.size() == 3 || t.parts.size() == 4,
+                 "'" << t.text << "': adaptive threshold syntax: threshold:adaptive:K[:C]");
+    const std::string k = trim(t.parts[2]);
+    STRIPE_CHECK(k == "3" || k == "5", "'" << t.text << "': threshold:adaptive takes a window size of 3 or 5");
+    const double Cd = t.parts.size() > 3 ? parse_num(trim(t.parts[3]), t.text) : 0.0;
+    STRIPE_CHECK(Cd == std::nearbyint(Cd) && std::fabs(Cd) <= 255,
+                 "'" << t.text << "': threshold:adaptive offset must be an integer in [-255, 255]");
+    t.expansion = "hold,box" + k + t.border + ",above:" + std::to_string((int)Cd);
+  } else if (mode == "otsu") {  // Otsu's level of the global histogram, chosen at run time (filters.h)
+    STRIPE_CHECK(t.parts.size() == 2, "'" << t.text << "': threshold:otsu takes no further arguments");
+    set_op(op, OpKind::Stat, "threshold:otsu");
+    op.stat = StatKind::Otsu;
+  } else {
+    op.kind = OpKind::Threshold;
+    op.ival = t.parts.size() > 1 ? (int)parse_num(t.parts[1], t.text) : 128;
+    op.text = "threshold:" + std::to_string(op.ival);
+  }
+}
+
+void p_equalize(Token& t, Op& op) {
+  no_arguments(t, "equalize");
+  set_op(op, OpKind::Stat, "equalize");
+  op.stat = StatKind::Equalize;
+}
+
+void p_autocontrast(Token& t, Op& op) {
+  // autocontrast[:P]  P percent of the pixels clipped at each end, in hundredths
+  STRIPE_CHECK(t.parts.size() <= 2, "'" << t.text << "': autocontrast syntax: autocontrast[:P]");
+  const double P = t.parts.size() > 1 ? parse_num(trim(t.parts[1]), t.text) : 0.0;
+  STRIPE_CHECK(P >= 0.0 && P < 50.0, "'" << t.text << "': autocontrast clips 0 <= P < 50 percent per end");
+  op.kind = OpKind::Stat;
+  op.stat = StatKind::AutoContrast;
+  op.ival = (int)std::nearbyint(100.0 * P);
+  STRIPE_CHECK(op.ival < 5000, "'" << t.text << "': autocontrast clips 0 <= P < 50 percent per end");
+  std::ostringstream os;
+  os << "autocontrast";
+  if (op.ival != 0) os << ":" << op.ival / 100.0;
+  op.text = os.str();
+}
+
+// ---- float convolutions ----
+void p_blur(Token& t, Op& op) {  // blur[:K[:sigma]][:exact|:lsb]
+  op.conv_digits = take_precision(t.parts);
+  STRIPE_CHECK(t.parts.size() <= 3, "blur syntax: blur:K[:sigma][:exact|:lsb]");
+  const int K = t.parts.size() > 1 ? (int)parse_num(t.parts[1], t.text) : 31;
+  const double sigma = t.parts.size() > 2 ? parse_num(t.parts[2], t.text) : 0.0;
+  STRIPE_CHECK(K >= 3 && K % 2 == 1 && K / 2 <= kMaxRadius,
+               "blur:K needs odd K in [3, " << 2 * kMaxRadius + 1 << "], got " << K);
+  op.kind = OpKind::Conv;
+  op.K = K;
+  const auto g = gaussian_1d(K, sigma);
+  op.weights.resize((size_t)K * K);
+  for (int i = 0; i < K; ++i)
+    for (int j = 0; j < K; ++j) op.weights[(size_t)i * K + j] = (float)(g[i] * g[j]);
+  op.sep_h.assign(g.begin(), g.end());
+  op.sep_v = op.sep_h;
+  op.text = t.text;
+}
+
+void p_conv(Token& t, Op& op) {
+  // conv:K:w00;w01;...[:exact|:lsb]  (K*K weights, row-major, correlation)
+  STRIPE_CHECK(t.parts.size() == 3 || t.parts.size() == 4, "conv syntax: conv:K:w0;w1;...;w(K*K-1)[:exact|:lsb]");
+  if (t.parts.size() == 4) {
+    const std::string prec = trim(t.parts[3]);
+    STRIPE_CHECK(prec == "exact" || prec == "lsb", "conv precision must be exact or lsb, got '" << prec << "'");
+    op.conv_digits = prec == "lsb" ? 2 : 3;
+  }
+  op.kind = OpKind::Conv;
+  op.K = (int)parse_num(t.parts[1], t.text);
+  STRIPE_CHECK(op.K >= 1 && op.K % 2 == 1 && op.K / 2 <= kMaxRadius, "conv K must be odd <= 33");
+  for (const auto& w : split(t.parts[2], ';')) op.weights.push_back((float)parse_num(trim(w), t.text));
+  STRIPE_CHECK((int)op.weights.size() == op.K * op.K,
+               "conv:" << op.K << " needs " << op.K * op.K << " weights, got " << op.weights.size());
+  op.text = t.text;
+}
+
+void p_sepconv(Token& t, Op& op) {
+  // sepconv:K:h0;...;h(K-1):v0;...;v(K-1)[:exact|:lsb]  rank-one KxK correlation
+  // weights[dy][dx] = v[dy] * h[dx] (separable MFMA path on the GPU)
+  op.conv_digits = take_precision(t.parts);
+  STRIPE_CHECK(t.parts.size() == 4, "sepconv syntax: sepconv:K:h0;...;h(K-1):v0;...;v(K-1)[:exact|:lsb]");
+  op.kind = OpKind::Conv;
+  op.K = (int)parse_num(t.parts[1], t.text);
+  STRIPE_CHECK(op.K >= 1 && op.K % 2 == 1 && op.K / 2 <= kMaxRadius, "sepconv K must be odd <= 33");
+  for (const auto& w : split(t.parts[2], ';')) op.sep_h.push_back((float)parse_num(trim(w), t.text));
+  for (const auto& w : split(t.parts[3], ';')) op.sep_v.push_back((float)parse_num(trim(w), t.text));
+  STRIPE_CHECK((int)op.sep_h.size() == op.K && (int)op.sep_v.size() == op.K,
+               "sepconv:" << op.K << " needs " << op.K << " horizontal and " << op.K << " vertical weights");
+  op.weights.resize((size_t)op.K * op.K);
+  for (int i = 0; i < op.K; ++i)
+    for (int j = 0; j < op.K; ++j) op.weights[(size_t)i * op.K + j] = op.sep_v[(size_t)i] * op.sep_h[(size_t)j];
+  op.text = t.text;
+}
+
+// ---- colour matrices ----
+void p_colormatrix(Token& t, Op& op) {
+  // colormatrix:m00;m01;m02;m10;...;m22[:b0;b1;b2]  row-major, out_c = sum_k m[c][k] in_k + b_c
+  STRIPE_CHECK(t.parts.size() == 2 || t.parts.size() == 3,
+               "'" << t.text << "': colormatrix syntax: colormatrix:m00;m01;...;m22[:b0;b1;b2]");
+  double m[9], b[3] = {0, 0, 0};
+  const auto ms = split(t.parts[1], ';');
+  STRIPE_CHECK(ms.size() == 9, "'" << t.text << "': colormatrix needs 9 coefficients, got " << ms.size());
+  for (int i = 0; i < 9; ++i) m[i] = parse_num(trim(ms[(size_t)i]), t.text);
+  if (t.parts.size() == 3) {
+    const auto bs = split(t.parts[2], ';');
+    STRIPE_CHECK(bs.size() == 3, "'" << t.text << "': colormatrix takes 3 offsets, got " << bs.size());
+    for (int i = 0; i < 3; ++i) b[i] = parse_num(trim(bs[(size_t)i]), t.text);
+  }
+  set_color_matrix(op, m, b, t.text);
+  op.text = t.text;
+}
+
+void p_sepia(Token& t, Op& op) {
+  no_arguments(t, "sepia");
+  const double m[9] = {.393, .769, .189, .349, .686, .168, .272, .534, .131}, b[3] = {0, 0, 0};
+  set_color_matrix(op, m, b, t.text);
+  op.text = "sepia";
+}
+
+void p_swaprb(Token& t, Op& op) {
+  no_arguments(t, t.name());
+  const double m[9] = {0, 0, 1, 0, 1, 0, 1, 0, 0}, b[3] = {0, 0, 0};
+  set_color_matrix(op, m, b, t.text);
+  op.text = "swaprb";
+}
+
+void p_saturation(Token& t, Op& op) {
+  STRIPE_CHECK(t.parts.size() == 2, "'" << t.text << "': saturation needs a factor, e.g. saturation:1.5");
+  const double S = parse_num(trim(t.parts[1]), t.text);
+  // off-diagonals (1 - S) L_k; the diagonal takes what is left of 4096, so
+  // every row sums to exactly 1.0 and grey pixels are fixed points
+  const double L[3] = {.299, .587, .114};
+  op.kind = OpKind::ColorMatrix;
+  for (int c = 0; c < 3; ++c) {
+    int off = 0;
+    for (int k = 0; k < 3; ++k) {
+      if (k == c) continue;
+      const double q = std::nearbyint((1.0 - S) * L[k] * 4096.0);
+      STRIPE_CHECK(std::fabs(q) <= 32767, "'" << t.text << "': saturation factor out of range");
+      op.cm[3 * c + k] = (int)q;
+      off += (int)q;
+    }
+    op.cm[3 * c + c] = 4096 - off;
+    STRIPE_CHECK(std::abs(op.cm[3 * c + c]) <= 32767, "'" << t.text << "': saturation factor out of range");
+  }
+  op.fval = (float)S;
+  std::ostringstream os;
+  os << "saturation:" << op.fval;
+  op.text = os.str();
+}
+
+void p_ycbcr(Token& t, Op& op) {
+  // JFIF full-range RGB <-> YCbCr; the inverse folds the -128 terms into the offsets
+  const bool inv = t.parts.size() == 2 && trim(t.parts[1]) == "inv";
+  STRIPE_CHECK(t.parts.size() == 1 || inv, "'" << t.text << "': ycbcr syntax: ycbcr or ycbcr:inv");
+  if (!inv) {
+    const double m[9] = {.299, .587, .114, -.168736, -.331264, .5, .5, -.418688, -.081312};
+    const double b[3] = {0, 128, 128};
+    set_color_matrix(op, m, b, t.text);
+  } else {
+    const double m[9] = {1, 0, 1.402, 1, -.344136, -.714136, 1, 1.772, 0};
+    const double b[3] = {-1.402 * 128, .344136 * 128 + .714136 * 128, -1.772 * 128};
+    set_color_matrix(op, m, b, t.text);
+  }
+  op.text = inv ? "ycbcr:inv" : "ycbcr";
+}
+
+// In catalogue order.  A row without names documents spellings that another
+// entry parses (threshold) or that need none: the plain stencil names reach
+// p_stencil through STRIPE_STENCILS.
+const std::vector<Entry>& entries() {
+  static const std::vector<Entry> t = {
+      // pointwise
+      {{"gray", "grayscale", "grey"}, false, "gray[:ref|bt601]",
+       "grayscale (ref: kernel.cu:31-44 weights/truncation; bt601: OpenCV, kern.cpp:73)", p_gray},
+      {{"contrast"}, false, "contrast:F[:cv]",
+       "trunc(clamp(F*(p-128)+128)) (kernel.cu:49-58); ':cv' = OpenCV rounding (kern.cpp:74)", p_contrast},
+      {{"invert", "negate"}, false, "invert", "255 - p", p_invert},
+      {{"brightness", "bright"}, false, "brightness:D", "sat(p + D)", p_brightness},
+      {{"threshold"}, false, "threshold:T", "p >= T ? 255 : 0", p_threshold},
+      {{"expand", "gray2rgb"}, false, "expand", "gray -> 3 identical channels (GRAY2BGR, kernel.cu:210)", p_expand},
+      // colour matrices (3 -> 3 channels, Q12 fixed point: sat((q.p + qb + 2048) >> 12))
+      {{"colormatrix"}, false, "colormatrix:m00;m01;..;m22[:b0;b1;b2]",
+       "out_c = sum_k m[c][k] in_k + b_c on (R, G, B), row-major; |m| < 8, |b| <= 2048", p_colormatrix},
+      {{"sepia"}, false, "sepia", "the sepia tone matrix [[.393,.769,.189],[.349,.686,.168],[.272,.534,.131]]",
+       p_sepia},
+      {{"saturation", "saturate"}, false, "saturation:S (saturate:S)",
+       "mix with the BT.601 luma: 0 = gray, 1 = identity, > 1 = more colour; gray pixels stay", p_saturation},
+      {{"swaprb", "bgr"}, false, "swaprb (bgr)", "swap the R and B channels (RGB <-> BGR)", p_swaprb},
+      {{"ycbcr"}, false, "ycbcr / ycbcr:inv", "JFIF full-range RGB -> (Y, Cb, Cr) and back", p_ycbcr},
+      // statistic ops (filters.h): each costs one read-only histogram pass (k_hist), one small all-reduce and
+      // one host synchronisation
+      {{"equalize"}, false, "equalize",
+       "histogram equalisation (OpenCV equalizeHist, exact): v0 = first v with h[v] > 0, c0 = h[v0], "
+       "D = N - c0; D == 0: identity; else 0 for v < v0 and min(255, (510 (cdf[v] - c0) + D) / (2 D))",
+       p_equalize},
+      {{"autocontrast"}, false, "autocontrast[:P]",
+       "contrast stretch clipping P percent (0 <= P < 50, default 0) of the pixels per end: "
+       "Pq = nearbyint(100 P), cut = N Pq / 10000; lo = first v with cdf[v] > cut, hi = last v "
+       "with N - cdf[v-1] > cut; hi <= lo: identity; else 0 for v <= lo, 255 for v >= hi, "
+       "(510 (v - lo) + (hi - lo)) / (2 (hi - lo)) between",
+       p_autocontrast},
+      {{}, false, "threshold:otsu",
+       "p >= T ? 255 : 0 with Otsu's T: the smallest t in 1..255 maximising "
+       "(S0 N - n0 S)^2 / (n0 n1) in double (n0, S0: count and sum below t; one grey level: T = 1)",
+       nullptr},
+      // stencils
+      {{}, false, "emboss3 / emboss5", "kernel.cu:64-94 filters (3x3 and diagonal 5x5)", nullptr},
+      {{}, false, "gaussian3/5/7", "binomial Gaussian, integer, rounded", nullptr},
+      {{}, false, "box3 / box5", "box mean, rounded", nullptr},
+      {{}, false, "sharpen", "[[0,-1,0],[-1,5,-1],[0,-1,0]]", nullptr},
+      {{}, false, "laplace", "[[0,1,0],[1,-4,1],[0,1,0]]", nullptr},
+      {{}, false, "sobel", "sat(|Gx| + |Gy|)", nullptr},
+      {{}, false, "sobel_l2 / magnitude", "sat(round(sqrt(Gx^2 + Gy^2))), exact integer rounding", nullptr},
+      {{"median"}, true, "median3 / median5 (median)", "element K*K/2 of the sorted KxK window, per channel", p_rank},
+      {{"erode"}, true, "erode3 / erode5 (erode)",
+       "minimum of the KxK window; border pixels are window members "
+       "(@constant: the zeros outside the frame darken its edge)",
+       p_rank},
+      {{"dilate"}, true, "dilate3 / dilate5 (dilate)", "maximum of the KxK window", p_rank},
+      {{"open"}, true, "open3 / open5", "erodeK,dilateK (an @border suffix applies to both)", p_sized_sugar,
+       "erode#,dilate#"},
+      {{"close"}, true, "close3 / close5", "dilateK,erodeK", p_sized_sugar, "dilate#,erode#"},
+      {{"bilateral"}, true, "bilateral3[:S] / bilateral5[:S] (bilateral)",
+       "edge-preserving smoothing, per channel: binomial taps times "
+       "r[|p - centre|], r[d] = rint(255 exp(-d^2 / (2 S^2))), "
+       "out = (sum w p + D/2) / D exactly; S = range sigma in grey "
+       "levels, 0 < S <= 10000, default 25 (S >= 4096: gaussianK)",
+       p_bilateral},
+      {{"blur", "gblur"}, false, "blur:K[:sigma][:lsb]",
+       "KxK float Gaussian (separable MFMA path), K <= 33; :lsb = every output within 1 LSB, "
+       "2.5x fewer MFMAs",
+       p_blur},
+      {{"conv"}, false, "conv:K:w0;w1;...[:lsb]",
+       "generic KxK float correlation (MFMA path); :lsb = within 1 LSB, 2/3 of the MFMAs", p_conv},
+      {{"sepconv"}, false, "sepconv:K:h..:v..[:lsb]", "rank-one KxK float correlation v (x) h (separable MFMA path)",
+       p_sepconv},
+      {{}, false, "...@border", "per-stencil border: reflect101 | replicate | constant | skip", nullptr},
+      // two-image ops: X the current image, H the held one (same channels), every rule per byte
+      {{"hold", "save"}, false, "hold (save)",
+       "the current image also becomes the held image (moves no pixels; a second hold replaces the first)", p_hold},
+      {{"swap"}, false, "swap", "current and held exchange roles (moves no pixels)", p_swap},
+      {{"add"}, false, "add", "min(255, X + H)", p_combine},
+      {{"sub"}, false, "sub", "max(0, H - X)  (held minus current)", p_combine},
+      {{"rsub"}, false, "rsub", "max(0, X - H)", p_combine},
+      {{"absdiff"}, false, "absdiff", "|X - H|", p_combine},
+      {{"min", "max"}, false, "min / max", "byte minimum / maximum of X and H", p_combine},
+      {{"lincomb"}, false, "lincomb:a:b[:c]",
+       "sat((qa X + qb H + qc + 2048) >> 12), q = nearbyint(4096 .): |a|, |b| < 8, |c| <= 2048", p_lincomb},
+      {{"blend"}, false, "blend:t",
+       "lincomb with qa = nearbyint(4096 t), qb = 4096 - qa, 0 <= t <= 1 (equal images are fixed points)", p_blend},
+      {{"above"}, false, "above[:d]", "H - X + d > 0 ? 255 : 0, integer d in [-255, 255]", p_above},
+      {{"gradient"}, true, "gradient3 / gradient5", "morphological gradient: hold,dilateK,swap,erodeK,sub",
+       p_sized_sugar, "hold,dilate#,swap,erode#,sub"},
+      {{"tophat"}, true, "tophat3 / tophat5", "x - open(x): hold,openK,sub", p_sized_sugar, "hold,open#,sub"},
+      {{"blackhat"}, true, "blackhat3 / blackhat5", "close(x) - x: hold,closeK,rsub", p_sized_sugar,
+       "hold,close#,rsub"},
+      {{"unsharp"}, false, "unsharp[:S[:K]]",
+       "x + S (x - gaussianK(x)): hold,gaussianK,lincomb:-S:1+S; S in (0, 7) default 1, K in 3|5|7 "
+       "default 5; flat regions stay",
+       p_unsharp},
+      {{}, false, "threshold:adaptive:K[:C]",
+       "x > boxK(x) - C ? 255 : 0 (OpenCV ADAPTIVE_THRESH_MEAN_C): hold,boxK,above:C; K in 3|5", nullptr},
+      // presets: not catalogue rows
+      {{"ref-gpu"}, false, nullptr, nullptr, p_preset, "gray:ref,contrast:3.5,emboss3@skip"},
+      {{"ref-cpu"}, false, nullptr, nullptr, p_preset, "gray:bt601,contrast:3:cv,emboss3"},
+  };
+  return t;
+}
+
+const Entry* find_entry(const std::string& name) {
+  for (const Entry& e : entries())
+    for (const char* n : e.names)
+      if (e.sized ? name.compare(0, std::strlen(n), n) == 0 : name == n) return &e;
+  return nullptr;
+}
+
+}  // namespace
+
+std::vector<std::pair<std::string, std::string>> filter_catalogue() {
+  std::vector<std::pair<std::string, std::string>> rows;
+  for (const Entry& e : entries())
+    if (e.syntax) rows.emplace_back(e.syntax, e.about);
+  return rows;
 }
 
 std::vector<Op> parse_chain(const std::string& spec_in) {
@@ -283,334 +701,27 @@ std::vector<Op> parse_chain(const std::string& spec_in) {
   for (const std::string& raw : split(spec, ',')) {
     std::string tok = trim(raw);
     STRIPE_CHECK(!tok.empty(), "empty token in chain '" << spec << "'");
-    // presets (SURVEY Appendix A "presets") expand in place; halo/partition
-    // flags of a preset are applied by the callers (CLI / models.PRESETS)
-    if (tok == "ref-gpu" || tok == "ref-cpu") {
-      auto sub = parse_chain(tok == "ref-gpu" ? "gray:ref,contrast:3.5,emboss3@skip"
-                                              : "gray:bt601,contrast:3:cv,emboss3");
-      ops.insert(ops.end(), sub.begin(), sub.end());
-      continue;
-    }
     Op op;
     // optional per-op border override: name[:args]@border
-    auto at = tok.find('@');
+    const auto at = tok.find('@');
     if (at != std::string::npos) {
       op.has_border = true;
       op.border = parse_border(tok.substr(at + 1));
       tok = tok.substr(0, at);
     }
-    auto parts = split(tok, ':');
-    const std::string name = parts[0];
-    StencilId sid;
-    // rank filters come in sizes 3 and 5 only: say so, rather than "unknown filter"
-    for (const char* fam : {"median", "erode", "dilate", "open", "close"}) {
-      const std::string f = fam;
-      if (name.compare(0, f.size(), f) != 0) continue;
-      const std::string sz = name.substr(f.size());
-      const bool sugar = f == "open" || f == "close";
-      STRIPE_CHECK(sz == "3" || sz == "5" || (sz.empty() && !sugar),
-                   "'" << name << "': " << f << " takes a window size of 3 or 5 (" << f << "3, " << f << "5)");
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << f << " takes no arguments");
-    }
-    if (name == "open3" || name == "open5" || name == "close3" || name == "close5") {
-      // morphological opening = erode then dilate, closing = dilate then erode;
-      // an @border suffix applies to both ops
-      const std::string k(1, name.back());
-      const std::string suffix = op.has_border ? std::string("@") + border_name(op.border) : "";
-      const bool open = name[0] == 'o';
-      auto sub = parse_chain((open ? "erode" : "dilate") + k + suffix + "," + (open ? "dilate" : "erode") + k + suffix);
+    Token t{tok, split(tok, ':'), op.has_border ? std::string("@") + border_name(op.border) : "", nullptr, ""};
+    t.entry = find_entry(t.name());
+    (t.entry ? t.entry->parse : p_stencil)(t, op);
+    if (!t.expansion.empty()) {  // sugar and presets expand in place
+      const auto sub = parse_chain(t.expansion);
       ops.insert(ops.end(), sub.begin(), sub.end());
       continue;
-    }
-    // two-image sugar (filters.h): hold, the stencils with the token's @border, one combine op
-    {
-      const std::string suffix = op.has_border ? std::string("@") + border_name(op.border) : "";
-      std::string expansion;
-      for (const char* fam : {"gradient", "tophat", "blackhat"}) {
-        const std::string f = fam;
-        if (name.compare(0, f.size(), f) != 0) continue;
-        const std::string k = name.substr(f.size());
-        STRIPE_CHECK(k == "3" || k == "5",
-                     "'" << name << "': " << f << " takes a window size of 3 or 5 (" << f << "3, " << f << "5)");
-        STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << f << " takes no arguments");
-        if (f == "gradient") expansion = "hold,dilate" + k + suffix + ",swap,erode" + k + suffix + ",sub";
-        else if (f == "tophat") expansion = "hold,open" + k + suffix + ",sub";
-        else expansion = "hold,close" + k + suffix + ",rsub";
-      }
-      if (name == "unsharp") {
-        // unsharp[:S[:K]]  x + S (x - gaussianK(x)) in Q12: qa = -nearbyint(4096 S) on the blur, 4096 - qa on x
-        STRIPE_CHECK(parts.size() <= 3, "'" << tok << "': unsharp syntax: unsharp[:S[:K]]");
-        const double S = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 1.0;
-        const std::string k = parts.size() > 2 ? trim(parts[2]) : "5";
-        STRIPE_CHECK(S > 0.0 && S < 7.0, "'" << tok << "': unsharp amount must be in (0, 7)");
-        STRIPE_CHECK(k == "3" || k == "5" || k == "7", "'" << tok << "': unsharp blurs with gaussian3, 5 or 7");
-        const int qa = -(int)std::nearbyint(4096.0 * S);
-        STRIPE_CHECK(qa != 0 && 4096 - qa <= 32767, "'" << tok << "': unsharp amount must be in (0, 7)");
-        expansion = "hold,gaussian" + k + suffix + ",lincomb:" + q12_text(qa) + ":" + q12_text(4096 - qa);
-      }
-      if (name == "threshold" && parts.size() > 1 && trim(parts[1]) == "adaptive") {
-        // threshold:adaptive:K[:C]  x > boxK(x) - C
-        STRIPE_CHECK(parts.size() == 3 || parts.size() == 4,
-                     "'" << tok << "': adaptive threshold syntax: threshold:adaptive:K[:C]");
-        const std::string k = trim(parts[2]);
-        STRIPE_CHECK(k == "3" || k == "5", "'" << tok << "': threshold:adaptive takes a window size of 3 or 5");
-        const double Cd = parts.size() > 3 ? parse_num(trim(parts[3]), tok) : 0.0;
-        STRIPE_CHECK(Cd == std::nearbyint(Cd) && std::fabs(Cd) <= 255,
-                     "'" << tok << "': threshold:adaptive offset must be an integer in [-255, 255]");
-        expansion = "hold,box" + k + suffix + ",above:" + std::to_string((int)Cd);
-      }
-      if (!expansion.empty()) {
-        auto sub = parse_chain(expansion);
-        ops.insert(ops.end(), sub.begin(), sub.end());
-        continue;
-      }
-    }
-    if (name == "hold" || name == "save" || name == "swap") {
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
-      op.kind = name == "swap" ? OpKind::Swap : OpKind::Hold;
-      op.text = name == "swap" ? "swap" : "hold";
-    } else if (name == "add" || name == "sub" || name == "rsub" || name == "absdiff" || name == "min" ||
-               name == "max") {
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
-      op.kind = OpKind::Combine;
-      op.comb = name == "add"    ? CombineKind::Add
-                : name == "sub"  ? CombineKind::Sub
-                : name == "rsub" ? CombineKind::RSub
-                : name == "min"  ? CombineKind::Min
-                : name == "max"  ? CombineKind::Max
-                                 : CombineKind::AbsDiff;
-      op.text = name;
-    } else if (name == "lincomb" || name == "blend") {
-      // lincomb:a:b[:c] / blend:t  (Q12, filters.h); both spelled canonically as lincomb
-      op.kind = OpKind::Combine;
-      op.comb = CombineKind::LinComb;
-      if (name == "blend") {
-        STRIPE_CHECK(parts.size() == 2, "'" << tok << "': blend needs a weight, e.g. blend:0.25");
-        const double t = parse_num(trim(parts[1]), tok);
-        STRIPE_CHECK(t >= 0.0 && t <= 1.0, "'" << tok << "': blend weight must be in [0, 1]");
-        op.cq[0] = (int)std::nearbyint(4096.0 * t);
-        op.cq[1] = 4096 - op.cq[0];
-      } else {
-        STRIPE_CHECK(parts.size() == 3 || parts.size() == 4, "'" << tok << "': lincomb syntax: lincomb:a:b[:c]");
-        for (int i = 0; i < 2; ++i) {
-          const double a = parse_num(trim(parts[(size_t)i + 1]), tok);
-          const double q = std::nearbyint(a * 4096.0);
-          STRIPE_CHECK(std::fabs(q) <= 32767, "'" << tok << "': coefficient " << a << " out of range (|a| < 8)");
-          op.cq[i] = (int)q;
-        }
-        if (parts.size() == 4) {
-          const double c = parse_num(trim(parts[3]), tok);
-          STRIPE_CHECK(std::fabs(c) <= 2048, "'" << tok << "': offset " << c << " out of range (|c| <= 2048)");
-          op.cq[2] = (int)std::nearbyint(c * 4096.0);
-        }
-      }
-      op.text = "lincomb:" + q12_text(op.cq[0]) + ":" + q12_text(op.cq[1]) +
-                (op.cq[2] != 0 ? ":" + q12_text(op.cq[2]) : std::string());
-    } else if (name == "above") {
-      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': above syntax: above[:d]");
-      const double d = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 0.0;
-      STRIPE_CHECK(d == std::nearbyint(d) && std::fabs(d) <= 255,
-                   "'" << tok << "': above takes an integer offset in [-255, 255]");
-      op.kind = OpKind::Combine;
-      op.comb = CombineKind::Above;
-      op.ival = (int)d;
-      op.text = op.ival != 0 ? "above:" + std::to_string(op.ival) : std::string("above");
-    } else if (name == "gray" || name == "grayscale" || name == "grey") {
-      op.kind = OpKind::Gray;
-      op.gray = GrayMode::BT601;
-      if (parts.size() > 1) {
-        if (parts[1] == "ref") op.gray = GrayMode::Ref;
-        else if (parts[1] == "bt601" || parts[1] == "cv") op.gray = GrayMode::BT601;
-        else fail("gray mode must be ref|bt601, got '" + parts[1] + "'");
-      }
-      op.text = op.gray == GrayMode::Ref ? "gray:ref" : "gray:bt601";
-    } else if (name == "contrast") {
-      op.kind = OpKind::Contrast;
-      op.fval = parts.size() > 1 ? (float)parse_num(parts[1], tok) : 3.5f;
-      op.round = RoundMode::Trunc;
-      if (parts.size() > 2) {
-        if (parts[2] == "cv" || parts[2] == "round") op.round = RoundMode::Nearest;
-        else if (parts[2] == "ref" || parts[2] == "trunc") op.round = RoundMode::Trunc;
-        else fail("contrast rounding must be ref|cv, got '" + parts[2] + "'");
-      }
-      std::ostringstream os;
-      os << "contrast:" << op.fval << (op.round == RoundMode::Nearest ? ":cv" : "");
-      op.text = os.str();
-    } else if (name == "invert" || name == "negate") {
-      op.kind = OpKind::Invert;
-      op.text = "invert";
-    } else if (name == "brightness" || name == "bright") {
-      op.kind = OpKind::Brightness;
-      STRIPE_CHECK(parts.size() > 1, "brightness needs a delta, e.g. brightness:40");
-      op.ival = (int)parse_num(parts[1], tok);
-      op.text = "brightness:" + std::to_string(op.ival);
-    } else if (name == "threshold" && parts.size() > 1 && trim(parts[1]) == "otsu") {
-      // Otsu's level of the global histogram, chosen at run time (filters.h)
-      STRIPE_CHECK(parts.size() == 2, "'" << tok << "': threshold:otsu takes no further arguments");
-      op.kind = OpKind::Stat;
-      op.stat = StatKind::Otsu;
-      op.text = "threshold:otsu";
-    } else if (name == "threshold") {
-      op.kind = OpKind::Threshold;
-      op.ival = parts.size() > 1 ? (int)parse_num(parts[1], tok) : 128;
-      op.text = "threshold:" + std::to_string(op.ival);
-    } else if (name == "equalize") {
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': equalize takes no arguments");
-      op.kind = OpKind::Stat;
-      op.stat = StatKind::Equalize;
-      op.text = "equalize";
-    } else if (name == "autocontrast") {
-      // autocontrast[:P]  P percent of the pixels clipped at each end, in hundredths
-      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': autocontrast syntax: autocontrast[:P]");
-      const double P = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 0.0;
-      STRIPE_CHECK(P >= 0.0 && P < 50.0, "'" << tok << "': autocontrast clips 0 <= P < 50 percent per end");
-      op.kind = OpKind::Stat;
-      op.stat = StatKind::AutoContrast;
-      op.ival = (int)std::nearbyint(100.0 * P);
-      STRIPE_CHECK(op.ival < 5000, "'" << tok << "': autocontrast clips 0 <= P < 50 percent per end");
-      std::ostringstream os;
-      os << "autocontrast";
-      if (op.ival != 0) os << ":" << op.ival / 100.0;
-      op.text = os.str();
-    } else if (name == "expand" || name == "gray2rgb") {
-      op.kind = OpKind::Expand;
-      op.text = "expand";
-    } else if (name == "blur" || name == "gblur") {
-      // blur:K[:sigma][:exact|:lsb]
-      const int digits = take_precision(parts);
-      STRIPE_CHECK(parts.size() <= 3, "blur syntax: blur:K[:sigma][:exact|:lsb]");
-      const int K = parts.size() > 1 ? (int)parse_num(parts[1], tok) : 31;
-      const double sigma = parts.size() > 2 ? parse_num(parts[2], tok) : 0.0;
-      Op c = make_conv_blur(K, sigma, tok);
-      c.has_border = op.has_border;
-      c.border = op.border;
-      c.conv_digits = digits;
-      op = c;
-    } else if (name == "conv") {
-      // conv:K:w00;w01;...[:exact|:lsb]  (K*K weights, row-major, correlation)
-      STRIPE_CHECK(parts.size() == 3 || parts.size() == 4, "conv syntax: conv:K:w0;w1;...;w(K*K-1)[:exact|:lsb]");
-      if (parts.size() == 4) {
-        const std::string prec = trim(parts[3]);
-        STRIPE_CHECK(prec == "exact" || prec == "lsb", "conv precision must be exact or lsb, got '" << prec << "'");
-        op.conv_digits = prec == "lsb" ? 2 : 3;
-      }
-      op.kind = OpKind::Conv;
-      op.K = (int)parse_num(parts[1], tok);
-      STRIPE_CHECK(op.K >= 1 && op.K % 2 == 1 && op.K / 2 <= kMaxRadius, "conv K must be odd <= 33");
-      for (const auto& w : split(parts[2], ';')) op.weights.push_back((float)parse_num(trim(w), tok));
-      STRIPE_CHECK((int)op.weights.size() == op.K * op.K,
-                   "conv:" << op.K << " needs " << op.K * op.K << " weights, got " << op.weights.size());
-      op.text = tok;
-    } else if (name == "sepconv") {
-      // sepconv:K:h0;...;h(K-1):v0;...;v(K-1)[:exact|:lsb]  rank-one KxK correlation
-      // weights[dy][dx] = v[dy] * h[dx] (separable MFMA path on the GPU)
-      op.conv_digits = take_precision(parts);
-      STRIPE_CHECK(parts.size() == 4, "sepconv syntax: sepconv:K:h0;...;h(K-1):v0;...;v(K-1)[:exact|:lsb]");
-      op.kind = OpKind::Conv;
-      op.K = (int)parse_num(parts[1], tok);
-      STRIPE_CHECK(op.K >= 1 && op.K % 2 == 1 && op.K / 2 <= kMaxRadius, "sepconv K must be odd <= 33");
-      for (const auto& w : split(parts[2], ';')) op.sep_h.push_back((float)parse_num(trim(w), tok));
-      for (const auto& w : split(parts[3], ';')) op.sep_v.push_back((float)parse_num(trim(w), tok));
-      STRIPE_CHECK((int)op.sep_h.size() == op.K && (int)op.sep_v.size() == op.K,
-                   "sepconv:" << op.K << " needs " << op.K << " horizontal and " << op.K << " vertical weights");
-      op.weights.resize((size_t)op.K * op.K);
-      for (int i = 0; i < op.K; ++i)
-        for (int j = 0; j < op.K; ++j) op.weights[(size_t)i * op.K + j] = op.sep_v[(size_t)i] * op.sep_h[(size_t)j];
-      op.text = tok;
-    } else if (name == "colormatrix") {
-      // colormatrix:m00;m01;m02;m10;...;m22[:b0;b1;b2]  row-major, out_c = sum_k m[c][k] in_k + b_c
-      STRIPE_CHECK(parts.size() == 2 || parts.size() == 3,
-                   "'" << tok << "': colormatrix syntax: colormatrix:m00;m01;...;m22[:b0;b1;b2]");
-      double m[9], b[3] = {0, 0, 0};
-      const auto ms = split(parts[1], ';');
-      STRIPE_CHECK(ms.size() == 9, "'" << tok << "': colormatrix needs 9 coefficients, got " << ms.size());
-      for (int i = 0; i < 9; ++i) m[i] = parse_num(trim(ms[(size_t)i]), tok);
-      if (parts.size() == 3) {
-        const auto bs = split(parts[2], ';');
-        STRIPE_CHECK(bs.size() == 3, "'" << tok << "': colormatrix takes 3 offsets, got " << bs.size());
-        for (int i = 0; i < 3; ++i) b[i] = parse_num(trim(bs[(size_t)i]), tok);
-      }
-      set_color_matrix(op, m, b, tok);
-      op.text = tok;
-    } else if (name == "sepia") {
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': sepia takes no arguments");
-      const double m[9] = {.393, .769, .189, .349, .686, .168, .272, .534, .131}, b[3] = {0, 0, 0};
-      set_color_matrix(op, m, b, tok);
-      op.text = "sepia";
-    } else if (name == "swaprb" || name == "bgr") {
-      STRIPE_CHECK(parts.size() == 1, "'" << tok << "': " << name << " takes no arguments");
-      const double m[9] = {0, 0, 1, 0, 1, 0, 1, 0, 0}, b[3] = {0, 0, 0};
-      set_color_matrix(op, m, b, tok);
-      op.text = "swaprb";
-    } else if (name == "saturation" || name == "saturate") {
-      STRIPE_CHECK(parts.size() == 2, "'" << tok << "': saturation needs a factor, e.g. saturation:1.5");
-      const double S = parse_num(trim(parts[1]), tok);
-      // off-diagonals (1 - S) L_k; the diagonal takes what is left of 4096, so
-      // every row sums to exactly 1.0 and grey pixels are fixed points
-      const double L[3] = {.299, .587, .114};
-      op.kind = OpKind::ColorMatrix;
-      for (int c = 0; c < 3; ++c) {
-        int off = 0;
-        for (int k = 0; k < 3; ++k) {
-          if (k == c) continue;
-          const double q = std::nearbyint((1.0 - S) * L[k] * 4096.0);
-          STRIPE_CHECK(std::fabs(q) <= 32767, "'" << tok << "': saturation factor out of range");
-          op.cm[3 * c + k] = (int)q;
-          off += (int)q;
-        }
-        op.cm[3 * c + c] = 4096 - off;
-        STRIPE_CHECK(std::abs(op.cm[3 * c + c]) <= 32767, "'" << tok << "': saturation factor out of range");
-      }
-      op.fval = (float)S;
-      std::ostringstream os;
-      os << "saturation:" << op.fval;
-      op.text = os.str();
-    } else if (name == "ycbcr") {
-      // JFIF full-range RGB <-> YCbCr; the inverse folds the -128 terms into the offsets
-      const bool inv = parts.size() == 2 && trim(parts[1]) == "inv";
-      STRIPE_CHECK(parts.size() == 1 || inv, "'" << tok << "': ycbcr syntax: ycbcr or ycbcr:inv");
-      if (!inv) {
-        const double m[9] = {.299, .587, .114, -.168736, -.331264, .5, .5, -.418688, -.081312};
-        const double b[3] = {0, 128, 128};
-        set_color_matrix(op, m, b, tok);
-      } else {
-        const double m[9] = {1, 0, 1.402, 1, -.344136, -.714136, 1, 1.772, 0};
-        const double b[3] = {-1.402 * 128, .344136 * 128 + .714136 * 128, -1.772 * 128};
-        set_color_matrix(op, m, b, tok);
-      }
-      op.text = inv ? "ycbcr:inv" : "ycbcr";
-    } else if (name.compare(0, 9, "bilateral") == 0) {
-      // bilateral3[:S] / bilateral5[:S] / bilateral[:S]  (filters.h); S is the range sigma
-      const std::string sz = name.substr(9);
-      STRIPE_CHECK(sz.empty() || sz == "3" || sz == "5",
-                   "'" << name << "': bilateral takes a window size of 3 or 5 (bilateral3, bilateral5)");
-      STRIPE_CHECK(parts.size() <= 2, "'" << tok << "': bilateral syntax: bilateral3[:S], bilateral5[:S]");
-      const double S = parts.size() > 1 ? parse_num(trim(parts[1]), tok) : 25.0;
-      STRIPE_CHECK(S > 0.0 && S <= 10000.0, "'" << tok << "': the range sigma must be in (0, 10000]");
-      op.kind = OpKind::Stencil;
-      op.sid = sz == "3" ? StencilId::Bilateral3 : StencilId::Bilateral5;
-      op.sigma = S;
-      op.range = bilateral_range_table(S);
-      op.text = std::string(stencil_info(op.sid).name) + ":" + shortest_text(S);
-    } else if (stencil_from_name(name, &sid)) {
-      op.kind = OpKind::Stencil;
-      op.sid = sid;
-      op.text = stencil_info(sid).name;
-    } else {
-      fail("unknown filter '" + name +
-           "' (gray[:ref|bt601], contrast:F[:cv], invert, brightness:D, threshold:T, expand, "
-           "emboss3, emboss5, gaussian3/5/7, box3/5, sharpen, laplace, sobel, sobel_l2, median3/5, "
-           "erode3/5, dilate3/5, open3/5, close3/5, bilateral3/5[:S], blur:K[:sigma][:lsb], conv:K:w..[:lsb], sepconv:K:h..:v..[:lsb], "
-           "colormatrix:m00;..;m22[:b0;b1;b2], sepia, saturation:S, swaprb, ycbcr[:inv], "
-           "equalize, autocontrast[:P], threshold:otsu, "
-           "hold, swap, add, sub, rsub, absdiff, min, max, lincomb:a:b[:c], blend:t, above[:d], "
-           "gradient3/5, tophat3/5, blackhat3/5, unsharp[:S[:K]], threshold:adaptive:K[:C])");
     }
     STRIPE_CHECK(op.kind != OpKind::Stat || !op.has_border,
                  "'" << raw << "': " << op.text << " is a pointwise op and takes no @border");
     STRIPE_CHECK(!(op.slot() || op.kind == OpKind::Combine) || !op.has_border,
                  "'" << raw << "': " << op.text << " reads no border and takes no @border");
-    if (op.has_border) op.text += std::string("@") + border_name(op.border);
+    op.text += t.border;
     ops.push_back(op);
   }
   return ops;

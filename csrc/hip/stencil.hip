@@ -6,7 +6,7 @@
 namespace stripe {
 namespace dev {
 
-STRIPE_STENCIL_FILTERS(STRIPE_EXTERN_LAUNCH_FILTER)
+STRIPE_STENCILS(STRIPE_EXTERN_LAUNCH_FILTER)
 
 // ------------------------------------------------------------------------------
 // Small general convolutions (conv:K, K <= 7, arbitrary float weights)
@@ -187,9 +187,9 @@ void launch_stencil(const Pass& p, const PassConsts& pc, const PassLaunch& L, hi
   const dev::BandLaunch B{tiles, n0, n1, L.band, sp.nt_stores, L.wgs, L.order, s};
   using namespace sdef;
   switch (p.sid) {
-#define STRIPE_LAUNCH_CASE(F) \
+#define STRIPE_LAUNCH_CASE(F, ...) \
   case StencilId::F: dev::launch_filter<F>(p, a, B); break;
-    STRIPE_STENCIL_FILTERS(STRIPE_LAUNCH_CASE)
+    STRIPE_STENCILS(STRIPE_LAUNCH_CASE)
 #undef STRIPE_LAUNCH_CASE
     default: fail("unknown stencil");
   }
@@ -211,9 +211,9 @@ bool sep_order_supported(const Pass& p) {
   if (p.kind != PassKind::Separable || p.pro.gray || p.pro.has_post || p.epi_expand) return false;
   using namespace sdef;
   switch (p.sid) {
-#define STRIPE_RUNS_CASE(F) \
+#define STRIPE_RUNS_CASE(F, ...) \
   case StencilId::F: return runs_capable<F>();
-    STRIPE_STENCIL_FILTERS(STRIPE_RUNS_CASE)
+    STRIPE_STENCILS(STRIPE_RUNS_CASE)
 #undef STRIPE_RUNS_CASE
     default: return false;
   }

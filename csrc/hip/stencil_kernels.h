@@ -1185,27 +1185,11 @@ inline int band_cap(const BandLaunch& B, policy::Family f, bool gray_prologue = 
 // Rank filters (sdef::RankDef: median / erode / dilate) have their own kernel
 // family, k_rank; launch_rank is defined in rank_kernels.h, which the unit
 // that instantiates those filters includes (stencil_inst_e.hip).
-template <class F, class = void>
-struct RankTag {
-  static constexpr int value = 0;
-};
-template <class F>
-struct RankTag<F, std::void_t<decltype(F::RANK)>> {
-  static constexpr int value = F::RANK;
-};
 template <int C, class F, int PRO, bool EXP>
 void launch_rank(bool skip, const KArgs& a, const BandLaunch& B);
 
 // Bilateral filters (sdef::BilateralDef) likewise: k_bilateral and
 // launch_bilateral are defined in bilateral_kernels.h (stencil_inst_f.hip).
-template <class F, class = void>
-struct BilateralTag {
-  static constexpr int value = 0;
-};
-template <class F>
-struct BilateralTag<F, std::void_t<decltype(F::BILATERAL)>> {
-  static constexpr int value = F::BILATERAL;
-};
 template <int C, class F, int PRO, bool EXP>
 void launch_bilateral(bool skip, const KArgs& a, const BandLaunch& B);
 
@@ -1245,9 +1229,9 @@ void launch_one(bool skip, const KArgs& a, BandLaunch B) {
       }
     }
   }
-  if constexpr (RankTag<F>::value != 0) {
+  if constexpr (F::RANK != 0) {
     launch_rank<C, F, PRO, EXP>(skip, a, B);
-  } else if constexpr (BilateralTag<F>::value != 0) {
+  } else if constexpr (F::BILATERAL != 0) {
     launch_bilateral<C, F, PRO, EXP>(skip, a, B);
   } else if constexpr (F::SEP) {
     const K fns[4] = {k_sep<C, F, PRO, false, 0, EXP>, k_sep<C, F, PRO, false, kNtAux, EXP>,
@@ -1285,13 +1269,11 @@ void launch_filter(const Pass& p, const KArgs& a, const BandLaunch& B) {
 }
 
 
-// Every filter F has launch_filter<F> compiled in exactly one stencil_inst_*.hip.
+// Every filter F of STRIPE_STENCILS (stencil_defs.h) has launch_filter<F>
+// compiled in exactly one stencil_inst_*.hip.
 #define STRIPE_LAUNCH_FILTER_SIG(F) void launch_filter<sdef::F>(const Pass&, const KArgs&, const BandLaunch&)
-#define STRIPE_EXTERN_LAUNCH_FILTER(F) extern template STRIPE_LAUNCH_FILTER_SIG(F);
+#define STRIPE_EXTERN_LAUNCH_FILTER(F, ...) extern template STRIPE_LAUNCH_FILTER_SIG(F);
 #define STRIPE_INSTANTIATE_LAUNCH_FILTER(F) template STRIPE_LAUNCH_FILTER_SIG(F);
-#define STRIPE_STENCIL_FILTERS(X) \
-  X(Emboss3) X(Emboss5) X(Sharpen) X(Laplace) X(Sobel) X(SobelL2) X(Gaussian3) X(Gaussian5) X(Gaussian7) X(Box3) \
-  X(Box5) X(Median3) X(Median5) X(Erode3) X(Erode5) X(Dilate3) X(Dilate5) X(Bilateral3) X(Bilateral5)
 
 }  // namespace dev
 }  // namespace stripe

@@ -1,6 +1,8 @@
 // Filter catalogue: the exact numeric specification of every operation
 // (SURVEY Appendix A).  Shared by the CPU golden path, the chain compiler and,
-// through stencil_defs.h, the HIP kernels.
+// through stencil_defs.h, the HIP kernels.  The spellings a chain token may
+// take, with a one-line description each, are the parser's token table
+// (filters.cpp, filter_catalogue); the stencil names are STRIPE_STENCILS.
 //
 // Reference filters:
 //   gray:ref      kernel.cu:31-44   Y = trunc(B*.11)+trunc(G*.59)+trunc(R*.3) (double)
@@ -94,9 +96,11 @@
 
 #include <array>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "stripe/common.h"
+#include "stripe/stencil_defs.h"
 
 namespace stripe {
 
@@ -139,26 +143,11 @@ struct Histogram {
 enum class GrayMode : int { BT601 = 0, Ref = 1 };
 enum class RoundMode : int { Trunc = 0, Nearest = 1 };
 
+// One value per row of STRIPE_STENCILS (stencil_defs.h), in its order.
 enum class StencilId : int {
-  Emboss3 = 0,
-  Emboss5,
-  Gaussian3,
-  Gaussian5,
-  Gaussian7,
-  Box3,
-  Box5,
-  Sharpen,
-  Laplace,
-  Sobel,
-  SobelL2,
-  Median3,
-  Median5,
-  Erode3,
-  Erode5,
-  Dilate3,
-  Dilate5,
-  Bilateral3,
-  Bilateral5,
+#define STRIPE_STENCIL_ID(Id, ...) Id,
+  STRIPE_STENCILS(STRIPE_STENCIL_ID)
+#undef STRIPE_STENCIL_ID
   kCount
 };
 
@@ -170,7 +159,8 @@ const char* rank_name(Rank r);
 
 struct StencilInfo {
   StencilId id;
-  const char* name;
+  const char* name;                // canonical spelling: names[0]
+  std::vector<const char*> names;  // every spelling (STRIPE_STENCILS)
   int K;                 // window size (odd)
   bool separable;        // weights = w1 (x) w1
   bool sobel;            // sat(|Gx|+|Gy|), or with l2: sat(round(sqrt(Gx^2 + Gy^2)))
@@ -219,6 +209,8 @@ struct Op {
 
 // Parse "gray:ref,contrast:3.5,emboss3" (also presets "ref-gpu", "ref-cpu").
 std::vector<Op> parse_chain(const std::string& spec);
+// The (syntax, one-line description) rows of the parser's token table, in its order.
+std::vector<std::pair<std::string, std::string>> filter_catalogue();
 std::string chain_to_string(const std::vector<Op>& ops);
 
 // Colour matrix arithmetic (the one definition every layer mirrors).

@@ -23,6 +23,7 @@ struct Emboss3 {
   static constexpr bool BINOM = false;
   static constexpr int K = 3, R = 1, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int w(int dy, int dx) {
     constexpr int t[9] = {-2, -1, 0, -1, 1, 1, 0, 1, 2};  // kernel.cu:71-75
     return t[dy * 3 + dx];
@@ -33,6 +34,7 @@ struct Emboss5 {
   static constexpr bool BINOM = false;
   static constexpr int K = 5, R = 2, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int w(int dy, int dx) {
     constexpr int d[5] = {4, 4, 1, -4, -4};  // kernel.cu:76-82 (diagonal)
     return dy == dx ? d[dy] : 0;
@@ -43,6 +45,7 @@ struct Sharpen {
   static constexpr bool BINOM = false;
   static constexpr int K = 3, R = 1, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int w(int dy, int dx) {
     constexpr int t[9] = {0, -1, 0, -1, 5, -1, 0, -1, 0};
     return t[dy * 3 + dx];
@@ -53,6 +56,7 @@ struct Laplace {
   static constexpr bool BINOM = false;
   static constexpr int K = 3, R = 1, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int w(int dy, int dx) {
     constexpr int t[9] = {0, 1, 0, 1, -4, 1, 0, 1, 0};
     return t[dy * 3 + dx];
@@ -66,6 +70,7 @@ struct Sobel {
   static constexpr bool BINOM = false;
   static constexpr int K = 3, R = 1, DIV = 1;
   static constexpr bool SEP = true, SOBEL = true;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int i) { return i == 1 ? 2 : 1; }
   STRIPE_HD static constexpr int wx(int dy, int dx) {
     constexpr int s[3] = {1, 2, 1}, d[3] = {-1, 0, 1};
@@ -91,6 +96,7 @@ struct Gaussian3 {  // binomial: cascade of K-1 two-tap sums
   static constexpr bool BINOM = true;
   static constexpr int K = 3, R = 1, DIV = 16;
   static constexpr bool SEP = true, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int i) {
     constexpr int t[3] = {1, 2, 1};
     return t[i];
@@ -102,6 +108,7 @@ struct Gaussian5 {  // binomial: cascade of K-1 two-tap sums
   static constexpr bool BINOM = true;
   static constexpr int K = 5, R = 2, DIV = 256;
   static constexpr bool SEP = true, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int i) {
     constexpr int t[5] = {1, 4, 6, 4, 1};
     return t[i];
@@ -113,6 +120,7 @@ struct Gaussian7 {  // binomial: cascade of K-1 two-tap sums
   static constexpr bool BINOM = true;
   static constexpr int K = 7, R = 3, DIV = 4096;
   static constexpr bool SEP = true, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int i) {
     constexpr int t[7] = {1, 6, 15, 20, 15, 6, 1};
     return t[i];
@@ -124,6 +132,7 @@ struct Box3 {
   static constexpr bool BINOM = false;
   static constexpr int K = 3, R = 1, DIV = 9;
   static constexpr bool SEP = true, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int) { return 1; }
   STRIPE_HD static constexpr int w(int, int) { return 1; }
 };
@@ -132,13 +141,15 @@ struct Box5 {
   static constexpr bool BINOM = false;
   static constexpr int K = 5, R = 2, DIV = 25;
   static constexpr bool SEP = true, SOBEL = false;
+  static constexpr int RANK = 0, BILATERAL = 0;
   STRIPE_HD static constexpr int g(int) { return 1; }
   STRIPE_HD static constexpr int w(int, int) { return 1; }
 };
 
 // Rank filters (erode = window minimum, dilate = maximum, median = element
 // K*K/2 of the sorted window): no weights, a compile-time rank tag instead.
-// The tags mirror stripe::Rank (filters.h).
+// The tags mirror stripe::Rank (filters.h).  Every definition carries RANK and
+// BILATERAL (0: a weighted stencil); they select the kernel family.
 constexpr int kRankMin = 1, kRankMax = 2, kRankMedian = 3;
 
 template <int K_, int RANK_>
@@ -146,7 +157,7 @@ struct RankDef {
   static constexpr bool BINOM = false;
   static constexpr int K = K_, R = K_ / 2, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
-  static constexpr int RANK = RANK_;
+  static constexpr int RANK = RANK_, BILATERAL = 0;
 };
 struct Median3 : RankDef<3, kRankMedian> {};
 struct Median5 : RankDef<5, kRankMedian> {};
@@ -163,7 +174,7 @@ struct BilateralDef {
   static constexpr bool BINOM = false;
   static constexpr int K = G::K, R = G::R, DIV = 1;
   static constexpr bool SEP = false, SOBEL = false;
-  static constexpr int BILATERAL = 1;
+  static constexpr int RANK = 0, BILATERAL = 1;
   STRIPE_HD static constexpr int g(int i) { return G::g(i); }
   STRIPE_HD static constexpr int w(int dy, int dx) { return G::g(dy) * G::g(dx); }
 };
@@ -172,3 +183,29 @@ struct Bilateral5 : BilateralDef<Gaussian5> {};
 
 }  // namespace sdef
 }  // namespace stripe
+
+// The one list of integer stencils: X(Id, "canonical name", aliases...), Id a
+// definition in sdef above.  The order is the StencilId order (filters.h), so
+// append.  From it come the enum, the info table and the name lookup
+// (filters.cpp), and the launcher's switch and extern templates (stencil.hip);
+// a new filter also needs its instantiation line in one stencil_inst_*.hip.
+#define STRIPE_STENCILS(X)                        \
+  X(Emboss3, "emboss3", "emboss")                 \
+  X(Emboss5, "emboss5")                           \
+  X(Gaussian3, "gaussian3")                       \
+  X(Gaussian5, "gaussian5", "gaussian", "gauss5") \
+  X(Gaussian7, "gaussian7")                       \
+  X(Box3, "box3")                                 \
+  X(Box5, "box5")                                 \
+  X(Sharpen, "sharpen")                           \
+  X(Laplace, "laplace", "laplacian")              \
+  X(Sobel, "sobel", "edge")                       \
+  X(SobelL2, "sobel_l2", "magnitude")             \
+  X(Median3, "median3", "median")                 \
+  X(Median5, "median5")                           \
+  X(Erode3, "erode3", "erode")                    \
+  X(Erode5, "erode5")                             \
+  X(Dilate3, "dilate3", "dilate")                 \
+  X(Dilate5, "dilate5")                           \
+  X(Bilateral3, "bilateral3")                     \
+  X(Bilateral5, "bilateral5", "bilateral")

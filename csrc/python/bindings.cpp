@@ -183,6 +183,12 @@ PYBIND11_MODULE(_C, m) {
     for (int v = 0; v < 256; ++v) lut[v] = apply_pointwise_u8(ops[0], (uint8_t)v);
     return lut;
   });
+  m.def("filter_catalogue", &filter_catalogue, "(syntax, description) rows of the parser's token table, in its order");
+  m.def("stencil_names", [] {
+    std::vector<std::string> names;
+    for (int i = 0; i < (int)StencilId::kCount; ++i) names.push_back(stencil_info((StencilId)i).name);
+    return names;
+  }, "canonical names of the integer stencils, in id order");
   m.def("stencil_weights", [](const std::string& name) {
     StencilId sid;
     STRIPE_CHECK(stencil_from_name(name, &sid), "unknown stencil " << name);

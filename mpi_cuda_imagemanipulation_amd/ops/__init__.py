@@ -27,73 +27,8 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-FILTERS = {
-    # pointwise
-    "gray[:ref|bt601]": "grayscale (ref: kernel.cu:31-44 weights/truncation; bt601: OpenCV, kern.cpp:73)",
-    "contrast:F[:cv]": "trunc(clamp(F*(p-128)+128)) (kernel.cu:49-58); ':cv' = OpenCV rounding (kern.cpp:74)",
-    "invert": "255 - p",
-    "brightness:D": "sat(p + D)",
-    "threshold:T": "p >= T ? 255 : 0",
-    "expand": "gray -> 3 identical channels (GRAY2BGR, kernel.cu:210)",
-    # colour matrices (3 -> 3 channels, Q12 fixed point: sat((q.p + qb + 2048) >> 12))
-    "colormatrix:m00;m01;..;m22[:b0;b1;b2]": "out_c = sum_k m[c][k] in_k + b_c on (R, G, B), row-major; |m| < 8, |b| <= 2048",
-    "sepia": "the sepia tone matrix [[.393,.769,.189],[.349,.686,.168],[.272,.534,.131]]",
-    "saturation:S (saturate:S)": "mix with the BT.601 luma: 0 = gray, 1 = identity, > 1 = more colour; gray pixels stay",
-    "swaprb (bgr)": "swap the R and B channels (RGB <-> BGR)",
-    "ycbcr / ycbcr:inv": "JFIF full-range RGB -> (Y, Cb, Cr) and back",
-    # statistic ops: one per-byte table from the GLOBAL histogram of the image as it enters the op (the whole
-    # frame over all ranks); on RGB the three channel histograms are pooled, h[v] = sum_c hist[c][v], and the
-    # one table is applied to all channels (no hue shift).  N = sum h, cdf[v] = sum_{u<=v} h[u], u64 integers.
-    # Each costs one read-only histogram pass (k_hist), one small all-reduce and one host synchronisation.
-    "equalize": "histogram equalisation (OpenCV equalizeHist, exact): v0 = first v with h[v] > 0, c0 = h[v0], "
-                "D = N - c0; D == 0: identity; else 0 for v < v0 and min(255, (510 (cdf[v] - c0) + D) / (2 D))",
-    "autocontrast[:P]": "contrast stretch clipping P percent (0 <= P < 50, default 0) of the pixels per end: "
-                        "Pq = nearbyint(100 P), cut = N Pq / 10000; lo = first v with cdf[v] > cut, hi = last v "
-                        "with N - cdf[v-1] > cut; hi <= lo: identity; else 0 for v <= lo, 255 for v >= hi, "
-                        "(510 (v - lo) + (hi - lo)) / (2 (hi - lo)) between",
-    "threshold:otsu": "p >= T ? 255 : 0 with Otsu's T: the smallest t in 1..255 maximising "
-                      "(S0 N - n0 S)^2 / (n0 n1) in double (n0, S0: count and sum below t; one grey level: T = 1)",
-    # stencils
-    "emboss3 / emboss5": "kernel.cu:64-94 filters (3x3 and diagonal 5x5)",
-    "gaussian3/5/7": "binomial Gaussian, integer, rounded",
-    "box3 / box5": "box mean, rounded",
-    "sharpen": "[[0,-1,0],[-1,5,-1],[0,-1,0]]",
-    "laplace": "[[0,1,0],[1,-4,1],[0,1,0]]",
-    "sobel": "sat(|Gx| + |Gy|)",
-    "sobel_l2 / magnitude": "sat(round(sqrt(Gx^2 + Gy^2))), exact integer rounding",
-    "median3 / median5 (median)": "element K*K/2 of the sorted KxK window, per channel",
-    "erode3 / erode5 (erode)": "minimum of the KxK window; border pixels are window members "
-                               "(@constant: the zeros outside the frame darken its edge)",
-    "dilate3 / dilate5 (dilate)": "maximum of the KxK window",
-    "open3 / open5": "erodeK,dilateK (an @border suffix applies to both)",
-    "close3 / close5": "dilateK,erodeK",
-    "bilateral3[:S] / bilateral5[:S] (bilateral)": "edge-preserving smoothing, per channel: binomial taps times "
-                                                   "r[|p - centre|], r[d] = rint(255 exp(-d^2 / (2 S^2))), "
-                                                   "out = (sum w p + D/2) / D exactly; S = range sigma in grey "
-                                                   "levels, 0 < S <= 10000, default 25 (S >= 4096: gaussianK)",
-    "blur:K[:sigma][:lsb]": "KxK float Gaussian (separable MFMA path), K <= 33; :lsb = every output within 1 LSB, "
-                            "2.5x fewer MFMAs",
-    "conv:K:w0;w1;...[:lsb]": "generic KxK float correlation (MFMA path); :lsb = within 1 LSB, 2/3 of the MFMAs",
-    "sepconv:K:h..:v..[:lsb]": "rank-one KxK float correlation v (x) h (separable MFMA path)",
-    "...@border": "per-stencil border: reflect101 | replicate | constant | skip",
-    # two-image ops: X the current image, H the held one (same channels), every rule per byte
-    "hold (save)": "the current image also becomes the held image (moves no pixels; a second hold replaces the first)",
-    "swap": "current and held exchange roles (moves no pixels)",
-    "add": "min(255, X + H)",
-    "sub": "max(0, H - X)  (held minus current)",
-    "rsub": "max(0, X - H)",
-    "absdiff": "|X - H|",
-    "min / max": "byte minimum / maximum of X and H",
-    "lincomb:a:b[:c]": "sat((qa X + qb H + qc + 2048) >> 12), q = nearbyint(4096 .): |a|, |b| < 8, |c| <= 2048",
-    "blend:t": "lincomb with qa = nearbyint(4096 t), qb = 4096 - qa, 0 <= t <= 1 (equal images are fixed points)",
-    "above[:d]": "H - X + d > 0 ? 255 : 0, integer d in [-255, 255]",
-    "gradient3 / gradient5": "morphological gradient: hold,dilateK,swap,erodeK,sub",
-    "tophat3 / tophat5": "x - open(x): hold,openK,sub",
-    "blackhat3 / blackhat5": "close(x) - x: hold,closeK,rsub",
-    "unsharp[:S[:K]]": "x + S (x - gaussianK(x)): hold,gaussianK,lincomb:-S:1+S; S in (0, 7) default 1, K in 3|5|7 "
-                       "default 5; flat regions stay",
-    "threshold:adaptive:K[:C]": "x > boxK(x) - C ? 255 : 0 (OpenCV ADAPTIVE_THRESH_MEAN_C): hold,boxK,above:C; K in 3|5",
-}
+# syntax -> one-line description of every chain token: the parser's own table (csrc/core/filters.cpp)
+FILTERS = dict(C.filter_catalogue())
 
 _cache_lock = threading.Lock()
 _engines: "collections.OrderedDict" = collections.OrderedDict()

@@ -44,7 +44,8 @@ def test_parser_errors_name_the_token(token, what):
 
 
 def test_unknown_filter_help_lists_it():
-    with pytest.raises(RuntimeError, match="bilateral3/5"):
+    # the message is assembled from the catalogue's syntax strings (ops.FILTERS keys)
+    with pytest.raises(RuntimeError, match=r"bilateral3\[:S\] / bilateral5\[:S\] \(bilateral\)"):
         C.parse_chain("nosuchfilter")
 
 

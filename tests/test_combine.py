@@ -159,8 +159,8 @@ def test_unknown_filter_lists_the_new_names():
         C.parse_chain("nonsuch")
     msg = str(e.value)
     for name in ["hold", "swap", "add", "sub", "rsub", "absdiff", "min", "max", "lincomb:a:b[:c]", "blend:t",
-                 "above[:d]", "gradient3/5", "tophat3/5", "blackhat3/5", "unsharp[:S[:K]]",
-                 "threshold:adaptive:K[:C]", "threshold:otsu", "median3/5"]:
+                 "above[:d]", "gradient3 / gradient5", "tophat3 / tophat5", "blackhat3 / blackhat5",
+                 "unsharp[:S[:K]]", "threshold:adaptive:K[:C]", "threshold:otsu", "median3 / median5"]:
         assert name in msg, name
     text = " ".join(m.ops.FILTERS)
     for name in ["hold", "swap", "absdiff", "lincomb", "blend", "above", "gradient3", "tophat3", "blackhat3",

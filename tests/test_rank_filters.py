@@ -73,7 +73,8 @@ def test_bad_sizes_rejected(C, bad):
 def test_unknown_filter_message_lists_rank_names(C):
     with pytest.raises(Exception) as ei:
         C.parse_chain("nosuchfilter")
-    for word in ("median3/5", "erode3/5", "dilate3/5", "open3/5", "close3/5"):
+    # the message is assembled from the catalogue's syntax strings (ops.FILTERS keys)
+    for word in ("median3 / median5", "erode3 / erode5", "dilate3 / dilate5", "open3 / open5", "close3 / close5"):
         assert word in str(ei.value)
 
 
