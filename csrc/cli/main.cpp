@@ -19,7 +19,7 @@
 //                [--frames F] [--json out.json]     (F: stream of F frames, resident scope)
 //   stripe cmp   a.ppm b.ppm [--tol 0]
 //   stripe gen   --synthetic WxHxC --seed S --output x.ppm
-//   stripe convert --input a.jpg --output b.ppm [--quality 95]
+//   stripe convert --input a.jpg --output b.ppm [--quality 95] [--resize WxH[:mode]]
 //   stripe info  [--chain ...] [--channels C] [--format json]
 #include <hip/hip_runtime.h>
 
@@ -35,7 +35,10 @@
 
 #include <unistd.h>
 
+#include "stripe/cpu_exec.h"
 #include "stripe/engine.h"
+#include "stripe/kernels.h"
+#include "stripe/resize.h"
 #include "stripe/trace.h"
 
 using namespace stripe;
@@ -247,6 +250,48 @@ Input read_input(const std::string& path, bool device) {
   return in;
 }
 
+// --resize WxH[:mode]: the frame is resized before the chain sees it (a stage in
+// front of the chain, like JPEG decode): on the GPU (k_resize) for device
+// backends, on cpu_resize for the host backend.
+Image resize_image(const Image& in, const ResizeSpec& r, bool on_device, int device) {
+  if (!on_device) return cpu_resize(in, r.W, r.H, r.mode, cpu_threads());
+  STRIPE_CHECK(r.W >= 1 && r.H >= 1, "resize: empty size");
+  HIP_CHECK(hipSetDevice(device));
+  Image out(r.W, r.H, in.C, NoInit{});
+  uint8_t *ds = nullptr, *dd = nullptr;
+  try {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
+    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
+    resize_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), r.W, r.H, r.mode, nullptr);
+    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipFree(ds);
+    (void)hipFree(dd);
+    throw;
+  }
+  HIP_CHECK(hipFree(ds));
+  HIP_CHECK(hipFree(dd));
+  return out;
+}
+
+// Applies --resize to the loaded input (a JPEG's coefficients are decoded to
+// pixels first); returns the JSON member that records the original size, or "".
+std::string resize_input(const Args& a, Input* in, bool on_device, int device) {
+  if (!a.has("resize")) return "";
+  const ResizeSpec r = parse_resize_spec(a.get("resize"));
+  const int W0 = in->W, H0 = in->H;
+  if (in->coefs) {
+    in->img = jpeg_pixels(std::move(in->jpeg));
+    in->jpeg = JpegCoefs{};
+    in->coefs = false;
+  }
+  in->img = resize_image(in->img, r, on_device, device);
+  in->W = in->img.W;
+  in->H = in->img.H;
+  return ",\"resized_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "]";
+}
+
 // One rank of a multi-process job: `stripe run --backend rccl --world N --rank r
 // --rendezvous FILE [--device d]` (like the reference's `mpiexec -n N`, one
 // process per rank; only rank 0 reads the input and writes the output).
@@ -258,9 +303,11 @@ int cmd_run_rank(const Args& a) {
   const int device = a.geti("device", ndev > 0 ? rank % ndev : 0);
   Input in;
   EngineConfig cfg;
+  std::string resized;
   if (rank == 0) {
     STRIPE_CHECK(a.has("input") && a.has("output"), "rank 0 needs --input and --output");
     in = read_input(a.get("input"), true);
+    resized = resize_input(a, &in, true, device);  // before the geometry is broadcast
     cfg = config_from(a, in.W, in.H, in.C);
   } else {
     cfg = config_from(a, 1, 1, 3);  // geometry arrives with the metadata broadcast
@@ -287,8 +334,8 @@ int cmd_run_rank(const Args& a) {
     if (is_jpeg_path(a.get("output"))) write_file_atomic(a.get("output"), jo.bytes);  // encoded from the root buffer
     else write_image(a.get("output"), out, a.geti("quality", 95));
     std::printf("{\"cmd\":\"run\",\"W\":%d,\"H\":%d,\"C\":%d,\"ranks\":%d,\"backend\":\"rccl\",\"processes\":%d,"
-                "\"chain\":\"%s\",\"wall_ms\":%.3f,\"kernel_ms\":%.4f,\"scatter_ms\":%.4f,\"gather_ms\":%.4f}\n",
-                in.W, in.H, in.C, world, world, cfg.chain.c_str(), ms, t.run, t.scatter, t.gather);
+                "\"chain\":\"%s\",\"wall_ms\":%.3f,\"kernel_ms\":%.4f,\"scatter_ms\":%.4f,\"gather_ms\":%.4f%s}\n",
+                in.W, in.H, in.C, world, world, cfg.chain.c_str(), ms, t.run, t.scatter, t.gather, resized.c_str());
   }
   return 0;
 }
@@ -298,7 +345,9 @@ int cmd_run(const Args& a) {
   STRIPE_CHECK(a.has("input") && a.has("output"), "run needs --input and --output");
   const bool host_run = a.get("backend", device_count() > 0 ? "local" : "host") == "host";
   const auto tr = std::chrono::steady_clock::now();
-  const Input in = read_input(a.get("input"), !host_run);
+  Input in = read_input(a.get("input"), !host_run);
+  const std::vector<int> rdevs = parse_int_list(a.get("devices"));
+  const std::string resized = resize_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]);
   const double read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
   EngineConfig cfg = config_from(a, in.W, in.H, in.C);
   const int N = a.geti("ranks", 1);
@@ -313,7 +362,9 @@ int cmd_run(const Args& a) {
     // --held FILE: a second image of equal size as the external held image (the
     // two-image form of the combine ops): one engine, no scatter / gather
     STRIPE_CHECK(N == 1, "--held is single-process only (--ranks 1), got --ranks " << N);
-    const Image held = read_image(a.get("held"));
+    Image held = read_image(a.get("held"));
+    if (a.has("resize"))  // the held image is resized the same way
+      held = resize_image(held, parse_resize_spec(a.get("resize")), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
     STRIPE_CHECK(held.W == cur.W && held.H == cur.H && held.C == cur.C,
                  "--held image is " << held.W << "x" << held.H << "x" << held.C << ", the input " << cur.W << "x"
@@ -332,8 +383,8 @@ int cmd_run(const Args& a) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     write_image(a.get("output"), out, a.geti("quality", 95));
     std::printf("{\"cmd\":\"run\",\"W\":%d,\"H\":%d,\"C\":%d,\"ranks\":1,\"backend\":\"%s\",\"chain\":\"%s\","
-                "\"held\":true,\"wall_ms\":%.3f,\"kernel_ms\":%.4f}\n",
-                in.W, in.H, in.C, backend.c_str(), cfg.chain.c_str(), ms, e.times().run);
+                "\"held\":true,\"wall_ms\":%.3f,\"kernel_ms\":%.4f%s}\n",
+                in.W, in.H, in.C, backend.c_str(), cfg.chain.c_str(), ms, e.times().run, resized.c_str());
     return 0;
   }
   Group g = make_group(backend, N, parse_int_list(a.get("devices")));
@@ -356,8 +407,9 @@ int cmd_run(const Args& a) {
   // read_ms / write_ms: the file stages around it (JPEG: entropy coding)
   std::printf("{\"cmd\":\"run\",\"W\":%d,\"H\":%d,\"C\":%d,\"ranks\":%d,\"backend\":\"%s\",\"chain\":\"%s\","
               "\"wall_ms\":%.3f,\"kernel_ms\":%.4f,\"scatter_ms\":%.4f,\"gather_ms\":%.4f,\"read_ms\":%.3f,"
-              "\"write_ms\":%.3f}\n",
-              in.W, in.H, in.C, N, backend.c_str(), cfg.chain.c_str(), ms, t.run, t.scatter, t.gather, read_ms, write_ms);
+              "\"write_ms\":%.3f%s}\n",
+              in.W, in.H, in.C, N, backend.c_str(), cfg.chain.c_str(), ms, t.run, t.scatter, t.gather, read_ms, write_ms,
+              resized.c_str());
   return 0;
 }
 
@@ -390,9 +442,15 @@ int cmd_gen(const Args& a) {
 // PPM/PGM <-> JPEG (input by content, output by extension)
 int cmd_convert(const Args& a) {
   STRIPE_CHECK(a.has("input") && a.has("output"), "convert needs --input and --output");
-  const Image img = read_image(a.get("input"));
+  Input in;
+  in.img = read_image(a.get("input"));
+  in.W = in.img.W, in.H = in.img.H, in.C = in.img.C;
+  const bool host_run = a.get("backend", device_count() > 0 ? "local" : "host") == "host";
+  const std::vector<int> devs = parse_int_list(a.get("devices"));
+  const std::string resized = resize_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]);
+  const Image& img = in.img;
   write_image(a.get("output"), img, a.geti("quality", 95));
-  std::printf("{\"cmd\":\"convert\",\"W\":%d,\"H\":%d,\"C\":%d}\n", img.W, img.H, img.C);
+  std::printf("{\"cmd\":\"convert\",\"W\":%d,\"H\":%d,\"C\":%d%s}\n", img.W, img.H, img.C, resized.c_str());
   return 0;
 }
 
@@ -715,6 +773,7 @@ void usage() {
                "        [--expand-gray] [--legacy-partition] [--iterations K] [--no-fuse] [--no-overlap]\n"
                "        [--dist-chunks K]  (> 1 ranks, single-pass chains: pipelined scatter/filter/gather)\n"
                "        [--held other.ppm]  (a second image of equal size, held for add/sub/absdiff/blend:t/...; --ranks 1)\n"
+               "        [--resize WxH[:auto|nearest|bilinear|area]]  (the frame, and --held's, resized before the chain)\n"
                "        one process per rank: --backend rccl --world N --rank r --rendezvous FILE [--device d]\n"
                "  bench --synthetic WxHxC [--seed S] [--chain C] [--ranks 1,2,4,8] [--iters N] [--warmup N]\n"
                "        [--scope resident|device,dist,e2e] [--backend rccl|local|host] [--json out.json]\n"
@@ -723,7 +782,7 @@ void usage() {
                "        [--halo-schedule auto|serial|overlap|pipeline|batched|serial+deep]  (frames at N > 1: auto times each)\n"
                "  cmp   a.ppm b.ppm [--tol T]\n"
                "  gen   --synthetic WxHxC [--seed S] --output out.ppm|out.jpg\n"
-               "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95]\n"
+               "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95] [--resize WxH[:mode]] [--backend host]\n"
                "  info  [--chain C] [--channels C] [--format json]\n");
 }
 

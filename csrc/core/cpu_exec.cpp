@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "stripe/rank_net.h"
+#include "stripe/resize.h"
 
 namespace stripe {
 
@@ -557,6 +558,80 @@ Image cpu_apply_plan(const Image& in, const Plan& plan, int threads, const Image
     src = &cur;
   }
   return cur;
+}
+
+// ---- resize (stripe/resize.h) ----
+namespace {
+// h'(y, .) of one source row: E2 = W2 * C values in 8.8 fixed point
+template <int C>
+void resize_hrow(const ResizeTaps& tx, const uint8_t* row, uint16_t* h) {
+  const int W2 = tx.n_out;
+  if (tx.max_count == 1) {
+    for (int ox = 0; ox < W2; ++ox) {
+      const uint8_t* p = row + (size_t)tx.first[(size_t)ox] * C;
+      for (int c = 0; c < C; ++c) h[(size_t)ox * C + c] = (uint16_t)(((uint32_t)kResizeOne * p[c] + 64) >> 7);
+    }
+    return;
+  }
+  for (int ox = 0; ox < W2; ++ox) {
+    const uint16_t* w = tx.w.data() + tx.offset[(size_t)ox];
+    const int n = tx.offset[(size_t)ox + 1] - tx.offset[(size_t)ox];
+    const uint8_t* p = row + (size_t)tx.first[(size_t)ox] * C;
+    uint32_t a[C] = {};
+    for (int u = 0; u < n; ++u)
+      for (int c = 0; c < C; ++c) a[c] += (uint32_t)w[u] * p[(size_t)u * C + c];
+    for (int c = 0; c < C; ++c) h[(size_t)ox * C + c] = (uint16_t)((a[c] + 64) >> 7);
+  }
+}
+
+STRIPE_SIMD void resize_vacc(uint32_t* acc, const uint16_t* h, uint32_t w, int n) {
+  for (int i = 0; i < n; ++i) acc[i] += w * h[i];
+}
+STRIPE_SIMD void resize_vout(const uint32_t* acc, uint8_t* out, int n) {
+  for (int i = 0; i < n; ++i) out[i] = (uint8_t)((acc[i] + (1u << 22)) >> 23);
+}
+}  // namespace
+
+void cpu_resize(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch, int W2,
+                int H2, ResizeMode mode, int threads) {
+  STRIPE_CHECK(C == 1 || C == 3, "resize: image must have 1 or 3 channels, got C = " << C);
+  STRIPE_CHECK(src && dst && W >= 1 && H >= 1, "resize: empty image");
+  STRIPE_CHECK(src_pitch >= (int64_t)W * C && dst_pitch >= (int64_t)W2 * C, "resize: pitch smaller than a row");
+  const ResizeTaps tx = resize_taps(W, W2, mode), ty = resize_taps(H, H2, mode);
+  const int E2 = W2 * C;
+  // a block's work is its source rows as much as its output rows
+  const int64_t row_bytes = (int64_t)E2 + (int64_t)W * C * std::max(1, H / H2);
+  parallel_rows(0, H2, row_bytes, std::max(1, threads), [&](int oa, int ob) {
+    // ring of the h' rows one output row needs; every source row of the block
+    // is reduced once, in order, when the first output row that reads it comes up
+    const int R = ty.max_count;
+    std::vector<uint16_t> ring((size_t)R * E2);
+    std::vector<uint32_t> acc((size_t)E2);
+    int next = ty.first[(size_t)oa];
+    for (int oy = oa; oy < ob; ++oy) {
+      const int f = ty.first[(size_t)oy], n = ty.count(oy);
+      next = std::max(next, f);
+      for (; next < f + n; ++next) {
+        uint16_t* h = ring.data() + (size_t)(next % R) * E2;
+        if (C == 1) resize_hrow<1>(tx, src + (int64_t)next * src_pitch, h);
+        else resize_hrow<3>(tx, src + (int64_t)next * src_pitch, h);
+      }
+      std::fill(acc.begin(), acc.end(), 0u);
+      for (int v = 0; v < n; ++v)
+        resize_vacc(acc.data(), ring.data() + (size_t)((f + v) % R) * E2, ty.w[(size_t)ty.offset[(size_t)oy] + v], E2);
+      resize_vout(acc.data(), dst + (int64_t)oy * dst_pitch, E2);
+    }
+  });
+}
+
+Image cpu_resize(const Image& in, int W2, int H2, ResizeMode mode, int threads) {
+  STRIPE_CHECK(in.C == 1 || in.C == 3, "resize: image must have 1 or 3 channels, got C = " << in.C);
+  STRIPE_CHECK(W2 >= 1 && W2 <= kResizeMaxSize && H2 >= 1 && H2 <= kResizeMaxSize,
+               "resize: size " << W2 << "x" << H2 << " outside 1.." << kResizeMaxSize);
+  Image out(W2, H2, in.C, NoInit{});
+  cpu_resize(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), W2, H2, mode,
+             threads);
+  return out;
 }
 
 }  // namespace stripe

@@ -100,6 +100,40 @@ void launch_histogram(const HistLaunch& L, hipStream_t s) {
   launch_hist_kernel(L, s);
 }
 
+void launch_resize(const ResizeLaunch& L, hipStream_t s) {
+  // host-side shape checks before the kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad resize launch: null src or dst");
+  STRIPE_CHECK(L.C == 1 || L.C == 3, "resize needs 1 or 3 channels, got C = " << L.C);
+  STRIPE_CHECK(L.W >= 1 && L.W <= kResizeMaxSize && L.H >= 1 && L.H <= kResizeMaxSize,
+               "resize: source size " << L.W << "x" << L.H << " outside 1.." << kResizeMaxSize);
+  STRIPE_CHECK(L.W2 >= 1 && L.W2 <= kResizeMaxSize && L.H2 >= 1 && L.H2 <= kResizeMaxSize,
+               "resize: destination size " << L.W2 << "x" << L.H2 << " outside 1.." << kResizeMaxSize);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "resize: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W2 * L.C,
+               "resize: dst_pitch " << L.dst_pitch << " < row bytes " << L.W2 * L.C);
+  STRIPE_CHECK(L.fx && L.ox && L.wx && L.fy && L.oy && L.wy, "resize: missing tap tables");
+  // the tile plan fits the instance it names (the kernel's LDS arrays)
+  STRIPE_CHECK(L.cls >= 0 && L.cls < 4 && L.tile >= 4 && L.tile <= kResizeTile && L.tile % 4 == 0,
+               "resize: bad tile plan (tile " << L.tile << ", class " << L.cls << ")");
+  const ResizeClass& rc = kResizeClasses[L.cls];
+  STRIPE_CHECK(L.max_span >= 1 && L.max_span + 15 <= rc.src_bytes && L.max_span <= L.W * L.C,
+               "resize: a tile's source span of " << L.max_span << " bytes does not fit class " << L.cls);
+  STRIPE_CHECK(rc.w_entries == 0 ? L.max_count_x <= 2 : L.max_weights <= rc.w_entries,
+               "resize: a tile's x-weights do not fit class " << L.cls);
+  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
+  // Where the caller names the allocations, the rows touched lie inside them.
+  if (L.src_base)
+    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
+                                            L.src_bytes,
+                 "resize: source rows outside their buffer");
+  if (L.dst_base)
+    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(L.H2 - 1) * L.dst_pitch +
+                                                (int64_t)L.W2 * L.C <= L.dst_bytes,
+                 "resize: destination rows outside their buffer");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_resize_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

@@ -178,6 +178,7 @@ enum class Family {
   ColorMix,       // k_colormix
   Blur,           // k_blur_pl
   Combine,        // k_combine
+  Resize,         // k_resize
 };
 
 struct PolicyIn {
@@ -188,6 +189,7 @@ struct PolicyIn {
   int wgs = -1;                     // PassLaunch::wgs
   bool gray_prologue = false;       // stencil with a gray prologue (3 input bytes per output byte)
   bool lut_stage = false;           // colour matrix with a pre or post LUT stage
+  int W2 = 0, rows2 = 0;            // resize: pixels per row and rows of the destination (W, rows: the source)
 };
 
 struct StreamPolicy {
@@ -224,7 +226,8 @@ constexpr int stencil_cap_default(Family f, bool gray_prologue) {
 //     output, which the size rule excludes as slow (partial lines);
 //   * all pointwise families and k_conv_small ignore PassLaunch::nt;
 //   * channel-changing pointwise applies its cap by size, whatever nt is;
-//   * the MFMA blur does not read STRIPE_NT.
+//   * the MFMA blur does not read STRIPE_NT;
+//   * resize has no occupancy cap and ignores PassLaunch::nt / wgs.
 inline StreamPolicy stream_policy(const PolicyIn& in) {
   StreamPolicy r;
   const int64_t px = (int64_t)in.rows * in.W;
@@ -303,6 +306,13 @@ inline StreamPolicy stream_policy(const PolicyIn& in) {
       if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
       r.cap = env_pw_wgs() != kKnobUnset ? env_pw_wgs() : kPwWgsCombine;
       r.cap_applied = r.cap > 0 && r.streaming && r.nt_stores;
+      break;
+    }
+    case Family::Resize: {
+      // one read of the source frame and one write of the destination, cin channels each
+      r.streaming = (px + (int64_t)in.rows2 * in.W2) * in.cin > dev::kNtMinBytes;
+      r.nt_stores = r.streaming;
+      if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
       break;
     }
     case Family::Blur: {

@@ -11,6 +11,7 @@
 
 #include "stripe/chain.h"
 #include "stripe/image.h"
+#include "stripe/resize.h"
 
 namespace stripe {
 
@@ -113,6 +114,53 @@ struct HistLaunch {
 constexpr int kHistBins = 256 * 3;  // bins of the device table (RGB; gray uses the first 256)
 void launch_histogram(const HistLaunch& L, hipStream_t s);    // dispatch.cpp: checks, then the kernel
 void launch_hist_kernel(const HistLaunch& L, hipStream_t s);  // histogram.hip
+
+// Resize of a whole frame (csrc/hip/resize.hip k_resize; the rule: stripe/resize.h).
+// Plain 64-bit addressing on arbitrary pitched buffers: no alignment of base
+// pointers or pitches is assumed, no byte outside [src, src + (H-1) pitch + W C)
+// is read and no byte outside the W2 * C bytes of each destination row is written.
+//
+// A workgroup owns `tile` output bytes (4 per thread) of kResizeBand output rows.
+// It stages the source bytes its tile reads, row by row, in LDS; the instance
+// (`cls`) fixes how many source bytes and x-weights fit:
+//   cls 0, 1: at most 2 taps per output pixel in x, weights in registers
+//   cls 2, 3: any tap count, the tile's x-weights in LDS
+constexpr int kResizeTile = 1024;  // largest tile, output bytes
+constexpr int kResizeBand = 8;     // output rows per workgroup
+struct ResizeClass {
+  int src_bytes;  // LDS bytes of one source row's span (15 of them are alignment slack)
+  int w_entries;  // LDS u16 entries of the tile's x-weights (0: registers)
+};
+constexpr ResizeClass kResizeClasses[4] = {{4608, 0}, {36864, 0}, {9216, 6144}, {36864, 12288}};
+struct ResizeLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int W = 0, H = 0, C = 0;
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+  int W2 = 0, H2 = 0;
+  // tap tables on the device (ResizeTaps::first / offset / w of each axis)
+  const int32_t *fx = nullptr, *ox = nullptr, *fy = nullptr, *oy = nullptr;
+  const uint16_t *wx = nullptr, *wy = nullptr;
+  // the tile plan of the x tables (resize_tile_plan) and what it measured on them
+  int tile = 0, cls = 0;
+  int max_count_x = 0;  // most taps of an output pixel in x
+  int max_span = 0;     // most source bytes a tile reads of one row
+  int max_weights = 0;  // most x-weights of a tile
+  // optional: the allocations the views lie in (checked against the rows touched)
+  const uint8_t* src_base = nullptr;
+  int64_t src_bytes = 0;
+  const uint8_t* dst_base = nullptr;
+  int64_t dst_bytes = 0;
+};
+// Largest tile (a multiple of 4 bytes, at most kResizeTile) and smallest class
+// that hold every tile's source span and weights; fills tile, cls, max_*.
+void resize_tile_plan(const ResizeTaps& tx, int C, ResizeLaunch* L);
+void launch_resize(const ResizeLaunch& L, hipStream_t s);         // dispatch.cpp: checks, then the kernel
+void launch_resize_kernel(const ResizeLaunch& L, hipStream_t s);  // resize.hip
+// Convenience: builds the two tap tables, uploads them on the stream and launches.
+void resize_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch, int W2,
+                   int H2, ResizeMode mode, hipStream_t s);
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

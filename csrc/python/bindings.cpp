@@ -301,14 +301,15 @@ PYBIND11_MODULE(_C, m) {
 
   // ---- launch policy (csrc/hip/launch_policy.h: pure host functions, no GPU) ----
   m.def("launch_policy", [](const std::string& family, int cin, int cout, int cmid, int W, int rows, int nt, int wgs,
-                            bool gray_prologue, bool lut_stage) {
+                            bool gray_prologue, bool lut_stage, int W2, int rows2) {
     static const std::pair<const char*, policy::Family> names[] = {
         {"sep", policy::Family::Sep},           {"sobel_rp", policy::Family::SobelRp},
         {"direct", policy::Family::Direct},     {"rank", policy::Family::Rank},
         {"bilateral", policy::Family::Bilateral},
         {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
-        {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine}};
+        {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine},
+        {"resize", policy::Family::Resize}};
     const policy::Family* f = nullptr;
     for (const auto& n : names)
       if (family == n.first) f = &n.second;
@@ -323,6 +324,8 @@ PYBIND11_MODULE(_C, m) {
     in.wgs = wgs;
     in.gray_prologue = gray_prologue;
     in.lut_stage = lut_stage;
+    in.W2 = W2;
+    in.rows2 = rows2;
     const policy::StreamPolicy r = policy::stream_policy(in);
     py::dict d;
     d["nt_stores"] = r.nt_stores;
@@ -333,9 +336,9 @@ PYBIND11_MODULE(_C, m) {
     return d;
   }, py::arg("family"), py::arg("cin") = 3, py::arg("cout") = 3, py::arg("cmid") = 3, py::arg("W") = 0,
      py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
-     py::arg("lut_stage") = false,
+     py::arg("lut_stage") = false, py::arg("W2") = 0, py::arg("rows2") = 0,
      "the launch decision of a kernel family: sep | sobel_rp | direct | rank | bilateral | conv_small | pointwise | "
-     "pointwise_flat | colormix | blur | combine");
+     "pointwise_flat | colormix | blur | combine | resize (W2, rows2: the destination of a resize)");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));
 
@@ -384,6 +387,60 @@ PYBIND11_MODULE(_C, m) {
     }
     return image_to_numpy(out);
   }, py::arg("image"), py::arg("chain"), py::arg("border") = "reflect101", py::arg("held") = py::none());
+
+  // ---- resize (stripe/resize.h): a stage in front of the chain, not a chain token ----
+  m.def("parse_resize_spec", [](const std::string& token) {
+    const ResizeSpec r = parse_resize_spec(token);
+    return py::make_tuple(r.W, r.H, std::string(resize_mode_name(r.mode)));
+  }, py::arg("spec"), "'WxH[:mode]' -> (W, H, mode)");
+  m.def("resize_taps", [](int n_in, int n_out, const std::string& mode) {
+    const ResizeTaps t = resize_taps(n_in, n_out, parse_resize_mode(mode));
+    py::array_t<int32_t> first((py::ssize_t)t.first.size()), count((py::ssize_t)t.first.size());
+    py::array_t<int32_t> w((py::ssize_t)t.w.size());
+    for (size_t i = 0; i < t.first.size(); ++i) {
+      first.mutable_data()[i] = t.first[i];
+      count.mutable_data()[i] = t.count((int)i);
+    }
+    for (size_t i = 0; i < t.w.size(); ++i) w.mutable_data()[i] = t.w[i];
+    return py::make_tuple(first, count, w);
+  }, py::arg("n_in"), py::arg("n_out"), py::arg("mode") = "auto",
+     "(first, count, weights): per output index the first input index and the tap count; the Q15 weights of all "
+     "outputs, concatenated in order");
+  m.def("golden_resize", [](const U8Array& a, int W2, int H2, const std::string& mode) {
+    const Image img = image_from_numpy(a);
+    const ResizeMode rm = parse_resize_mode(mode);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_resize(img, W2, H2, rm);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "auto");
+  m.def("cpu_resize", [](const U8Array& a, int W2, int H2, const std::string& mode, int threads) {
+    const Image img = image_from_numpy(a);
+    const ResizeMode rm = parse_resize_mode(mode);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_resize(img, W2, H2, rm, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "auto", py::arg("threads") = 0);
+  m.def("resize_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int C, uintptr_t dst, int64_t dst_pitch,
+                            int W2, int H2, const std::string& mode, uintptr_t stream) {
+    const ResizeMode rm = parse_resize_mode(mode);
+    py::gil_scoped_release nogil;
+    resize_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, C, reinterpret_cast<uint8_t*>(dst),
+                  dst_pitch, W2, H2, rm, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("C"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "auto", py::arg("stream") = 0,
+     "k_resize on pitched device buffers (any alignment), queued on the stream");
+  m.def("resize_tile", [] {
+    py::dict d;
+    d["tile"] = kResizeTile;
+    d["band"] = kResizeBand;
+    return d;
+  }, "k_resize's tile constants: output bytes per workgroup tile, output rows per band");
 
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },

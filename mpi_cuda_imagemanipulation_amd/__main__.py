@@ -5,6 +5,7 @@ gray -> contrast -> emboss, gather, write) is `run --preset ref-gpu`.
 
   python -m mpi_cuda_imagemanipulation_amd run --input in.jpg --output out.png \\
       --chain gray:ref,contrast:3.5,emboss3 --ranks 4 --backend local
+  python -m mpi_cuda_imagemanipulation_amd run --input in.jpg --output out.png --resize 1920x1080 --chain sharpen
   python -m mpi_cuda_imagemanipulation_amd convert in.jpg out.ppm
   python -m mpi_cuda_imagemanipulation_amd filters
 
@@ -50,6 +51,9 @@ def main(argv=None) -> int:
     r.add_argument("--row-weights", default=None,
                    help="comma list, one share per rank (weighted split, e.g. a larger root share for "
                         "--dist-chunks); default: even rows")
+    r.add_argument("--resize", default=None, metavar="WxH[:mode]",
+                   help="resize the loaded frame before the chain (mode: auto | nearest | bilinear | area); "
+                        "on the GPU for GPU backends, on the host executor for host / gloo")
     r.add_argument("--verbose", "-v", action="store_true", help="rank-prefixed progress log on stderr")
     c = sub.add_parser("convert", help="convert between image formats")
     c.add_argument("src")
@@ -82,6 +86,7 @@ def main(argv=None) -> int:
         import torch
 
         backend = "local" if torch.cuda.is_available() else "host"
+    img, resized_from = _resize_input(a, img, backend != "host")
     t0 = time.perf_counter()
     log = utils.get_logger("cli", 0)
     log.info("run %s on %s, %d ranks (%s)", pipe.spec.chain, img.shape, a.ranks, backend)
@@ -89,8 +94,29 @@ def main(argv=None) -> int:
     ms = (time.perf_counter() - t0) * 1e3
     utils.write_image(a.output, out)
     print(json.dumps({"cmd": "run", "input": a.input, "output": a.output, "shape": list(img.shape),
-                      "chain": pipe.spec.chain, "ranks": a.ranks, "backend": backend, "wall_ms": round(ms, 3)}))
+                      "chain": pipe.spec.chain, "ranks": a.ranks, "backend": backend, "wall_ms": round(ms, 3),
+                      **({"resized_from": resized_from} if resized_from else {})}))
     return 0
+
+
+def _resize_input(a, img, on_gpu):
+    """--resize WxH[:mode] on the loaded frame: (frame, [W, H] it had, or None)."""
+    if not a.resize:
+        return img, None
+    import numpy as np
+
+    from . import ops
+    from ._native import C
+
+    W2, H2, mode = C.parse_resize_spec(a.resize)
+    from_wh = [int(img.shape[1]), int(img.shape[0])]
+    if on_gpu:
+        import torch
+
+        out = ops.resize(torch.from_numpy(np.ascontiguousarray(img)).cuda(), size=(H2, W2), mode=mode).cpu().numpy()
+    else:
+        out = ops.resize(np.ascontiguousarray(img), size=(H2, W2), mode=mode)
+    return out, from_wh
 
 
 def _run_per_process(a, pipe) -> int:
@@ -104,6 +130,9 @@ def _run_per_process(a, pipe) -> int:
     ctx = parallel.init(a.backend)
     log = utils.get_logger("cli", ctx.rank)
     img = utils.read_image(a.input) if ctx.rank == 0 else None
+    resized_from = None
+    if ctx.rank == 0:  # rank 0 resizes before it broadcasts the geometry
+        img, resized_from = _resize_input(a, img, a.backend in ("rccl", "gloo-gpu"))
     meta = [None if img is None else tuple(img.shape)]
     if ctx.world > 1:
         dist.broadcast_object_list(meta, src=0)
@@ -131,7 +160,8 @@ def _run_per_process(a, pipe) -> int:
         utils.write_image(a.output, np.ascontiguousarray(out))
         print(json.dumps({"cmd": "run", "input": a.input, "output": a.output, "shape": list(shape),
                           "chain": pipe.spec.chain, "ranks": ctx.world, "backend": a.backend,
-                          "stripe_rows": dp.stripe[1], "dist_ms": round(ms, 3)}))
+                          "stripe_rows": dp.stripe[1], "dist_ms": round(ms, 3),
+                          **({"resized_from": resized_from} if resized_from else {})}))
     if ctx.world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -410,6 +410,82 @@ def maximum(x, y):
     return combine(x, y, "max")
 
 
+# ---- resize: a stage in front of the chain, not a chain token ---------------------
+RESIZE_MODES = ("auto", "nearest", "bilinear", "area")
+_MAX_SIZE = 65535
+
+
+def _resize_target(H, W, size, scale):
+    if (size is None) == (scale is None):
+        raise ValueError("resize needs exactly one of size=(H2, W2) and scale")
+    if size is not None:
+        try:
+            H2, W2 = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"size must be (H2, W2), got {size!r}") from None
+    else:
+        sy, sx = (scale, scale) if np.isscalar(scale) else scale
+        if not (sy > 0 and sx > 0):
+            raise ValueError(f"scale must be positive, got {scale!r}")
+        H2, W2 = max(1, int(np.rint(H * sy))), max(1, int(np.rint(W * sx)))
+    if not (1 <= H2 <= _MAX_SIZE and 1 <= W2 <= _MAX_SIZE):
+        raise ValueError(f"size must lie in 1..{_MAX_SIZE} per axis, got ({H2}, {W2})")
+    return H2, W2
+
+
+def resize(x, size=None, scale=None, mode: str = "auto"):
+    """Resize an image to size=(H2, W2), or by scale (a float or (sy, sx); n_out = max(1, rint(n * s))).
+
+    mode: "nearest", "bilinear" (half-pixel centres, no antialiasing), "area" (exact cell overlap,
+    shrinking axes only, factor <= 32) or "auto" (per axis: area where it shrinks, bilinear where it
+    grows).  One integer rule in every layer (`C.resize_taps`): CUDA uint8 tensors run on the k_resize
+    HIP kernel on torch's current stream, numpy arrays / CPU tensors on the threaded host executor,
+    bit-identical to `resize_reference`.  A BxHxWxC batch runs frame by frame."""
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"mode must be one of {RESIZE_MODES}, got {mode!r}")
+    if x.ndim == 4:
+        if x.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
+        H2, W2 = _resize_target(x.shape[1], x.shape[2], size, scale)
+        outs = [resize(x[b], (H2, W2), None, mode) for b in range(x.shape[0])]
+        if _is_tensor(x):
+            return torch.stack(outs) if outs else x.new_empty((0, H2, W2, x.shape[3]))
+        return np.stack(outs) if outs else np.empty((0, H2, W2, x.shape[3]), np.uint8)
+    W, H, Cc = _shape(x)
+    H2, W2 = _resize_target(H, W, size, scale)
+    if _is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        xc = x.contiguous()
+        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            C.resize_device(xc.data_ptr(), W * Cc, W, H, Cc, out.data_ptr(), W2 * Cc, W2, H2, mode,
+                            stream.cuda_stream)
+        # keep the input alive until the stream has consumed it
+        xc.record_stream(stream)
+        return out
+    was_tensor = _is_tensor(x)
+    arr = x.numpy() if was_tensor else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.cpu_resize(np.ascontiguousarray(arr[:, :, 0] if keep else arr), W2, H2, mode)
+    if keep:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if was_tensor else out
+
+
+def resize_reference(x, size=None, scale=None, mode: str = "auto"):
+    """Golden CPU result of `resize`: the rule as a plain per-pixel loop."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    W, H, _ = _shape(arr)
+    H2, W2 = _resize_target(H, W, size, scale)
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.golden_resize(np.ascontiguousarray(arr[:, :, 0] if keep else arr), W2, H2, mode)
+    return out[:, :, None] if keep else out
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -423,4 +499,5 @@ __all__ = [
     "histogram", "equalize", "autocontrast", "threshold_otsu", "otsu_level",
     "unsharp_mask", "morph_gradient", "top_hat", "black_hat", "adaptive_threshold",
     "combine", "absdiff", "add", "subtract", "blend", "minimum", "maximum",
+    "resize", "resize_reference", "RESIZE_MODES",
 ]

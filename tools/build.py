@@ -48,6 +48,7 @@ CORE_SOURCES = [
     "core/jpeg.cpp",
     "core/golden.cpp",
     "core/cpu_exec.cpp",
+    "core/resize.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -61,6 +62,7 @@ CORE_SOURCES = [
     "hip/jpeg_dev.hip",
     "hip/histogram.hip",
     "hip/combine.hip",
+    "hip/resize.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
