@@ -109,8 +109,7 @@ struct Plan {
   int held_c = 0;  // channels of an external held image the chain starts with (0: none)
   std::vector<Pass> passes;
   std::string describe() const;
-  // some pass holds, swaps or combines: the engine keeps a third stripe buffer,
-  // and every schedule that assumes a static two-buffer chain declines
+  // some pass holds, swaps or combines: the engine keeps a third stripe buffer
   bool branched() const {
     for (const Pass& p : passes)
       if (p.branches()) return true;
@@ -122,13 +121,19 @@ struct Plan {
       if (!p.slots.empty()) return true;
     return false;
   }
-  // some pass carries a statistic op: every schedule that assumes a static
-  // chain (deep halo, pipelined, graph replay, chunked transfers) declines
+  // some pass carries a statistic op (a table built from its input at run time)
   bool data_dependent() const {
     for (const Pass& p : passes)
       if (p.data_dependent()) return true;
     return false;
   }
+  // Every pass reads the current buffer and writes the other one of a ping-pong
+  // pair, with constants fixed at plan time.  The engine's deep halo and deep
+  // steps, its pipelined schedule, posted halos, graph replay and the chunked
+  // e2e / dist / to-host steps all rely on this and decline a plan without it.
+  // A new plan property that breaks the static two-buffer assumption belongs
+  // in this predicate, not at those sites.
+  bool static_chain() const { return !data_dependent() && !branched(); }
 };
 
 // default_border: border for every stencil without an explicit @mode suffix.

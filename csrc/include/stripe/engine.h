@@ -357,11 +357,27 @@ class Engine {
   bool self_halo_ = false;  // EngineConfig::self_halo, validated
   bool time_halo_ = true;  // record the halo stage events (last iteration of a run only)
   bool stage_timing_ = true;  // set_stage_timing
-  void run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint8_t* in2 = nullptr);
+  void run_pass(size_t pi, const uint8_t* in, uint8_t* out, const uint8_t* in2 = nullptr);
   // One pass of the chain on the engine's buffers: the pass's slot actions
   // (hold / swap: index changes), the pass from the current buffer (and the
   // held one) into a free buffer, which becomes current.
-  void step_pass(const Pass& p);
+  void step_pass(size_t pi);
+  // One or two output row ranges of a launch: {y0, y1} or {y0, y1, y2, y3}.
+  struct Rows {
+    Rows(int y0, int y1) : n(1), y{y0, y1, 0, 0} {}
+    Rows(int y0, int y1, int y2, int y3) : n(2), y{y0, y1, y2, y3} {}
+    int n;
+    int y[4];
+  };
+  // Launch pass `pi` over `r` from a prepared launch: every range field of the
+  // copy is written, so a launch inherits nothing from the one before it.
+  void launch_rows(size_t pi, PassLaunch L, Rows r, hipStream_t s);
+  // Rows `r` of pass `pi` on the engine's backend: make_launch + launch_rows on
+  // the device, cpu_pass (one range, `s` unused) on the host.  ext: halo rows
+  // the ranges may cover (PassLaunch::ext); resolved: a statistic pass as
+  // prepare_stat resolved it, which is what the host executes.
+  void run_rows(size_t pi, const uint8_t* in, uint8_t* out, Rows r, hipStream_t s, int ext = 0,
+                const uint8_t* in2 = nullptr, const Pass* resolved = nullptr);
   // the buffer a pass writes: the other one of the ping-pong pair, or (branched
   // plans) the one that is neither current nor held
   int free_buf() const;
@@ -382,10 +398,16 @@ class Engine {
   Buffer hist_dev_;          // device engine: the 256 x 3 u32 table k_hist adds to
   Buffer hist_stage_;        // all-reduce staging where the communicator's buffers live
   PinnedBuffer hist_host_;   // device engine: counts, LUT block and all-reduce staging on the host
+  // a single-pass Plan::static_chain(): what the pipelined, posted-halo and chunked steps take
+  bool one_static_pass() const { return plan_.passes.size() == 1 && plan_.static_chain(); }
   bool pipelined_ok() const;
   int chain_reach() const;  // sum of the chain's radii if every pass can extend its rows, else 0
   int choose_depth() const;
   void run_deep(int iterations);
+  // The passes of step i of an m-step deep block (run_deep, deep_step).
+  // overlap_first: the block's exchange is in flight on the comm stream
+  // (ev_[5]), so the first pass is split around the wait for it.
+  void deep_block_step(int m, int i, bool overlap_first = false);
   int depth_ = 0;                  // iterations per chain-level exchange (deep halo); 0: per-pass exchange
   void run_pipelined(int iterations);
   void join_d2h();
@@ -422,7 +444,8 @@ class Engine {
   std::vector<hipEvent_t> ev_h2d_, ev_cmp_;
   PinnedBuffer host_in_, host_out_;
   Buffer stage_in_, stage_out_;  // packed device staging rows of the e2e path
-  PassLaunch make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi, const uint8_t* in2 = nullptr) const;
+  void ensure_chunk_events(int n);  // ev_h2d_ and ev_cmp_ hold at least n events each
+  PassLaunch make_launch(size_t pi, const uint8_t* in, uint8_t* out, const uint8_t* in2 = nullptr) const;
   bool own_streams_ = false;   // s_comm_ (and the e2e streams) are ours
   bool own_compute_ = false;   // s_compute_ is ours (false after use_external_stream)
   hipEvent_t ev_[8] = {};

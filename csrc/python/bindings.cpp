@@ -295,6 +295,7 @@ PYBIND11_MODULE(_C, m) {
     d["passes"] = passes;
     d["data_dependent"] = p.data_dependent();
     d["branched"] = p.branched();
+    d["static_chain"] = p.static_chain();
     return d;
   }, py::arg("chain"), py::arg("cin") = 3, py::arg("border") = "reflect101", py::arg("fuse") = true,
      py::arg("held_channels") = 0);

@@ -602,8 +602,8 @@ void Engine::post_halo_ops(uint8_t* org, int C, int R, hipStream_t s) {
 }
 
 bool Engine::posts_halo() const {
-  return device() && comm_ && cfg_.halo && neighbours() && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
-         plan_.passes[0].R > 0 && stripe().rows > 0 && !plan_.data_dependent() && !plan_.branched();
+  return device() && comm_ && cfg_.halo && neighbours() && one_static_pass() && plan_.cin == plan_.cout &&
+         plan_.passes[0].R > 0 && stripe().rows > 0;
 }
 
 void Engine::post_halo() {
@@ -662,7 +662,8 @@ void Engine::run_posted() {
   halo_done_ = false;
 }
 
-PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, int pi, const uint8_t* in2) const {
+PassLaunch Engine::make_launch(size_t pi, const uint8_t* in, uint8_t* out, const uint8_t* in2) const {
+  const Pass& p = plan_.passes[pi];
   const RowGeom g = geom();
   PassLaunch L;
   L.in = in;
@@ -712,6 +713,26 @@ PassLaunch Engine::make_launch(const Pass& p, const uint8_t* in, uint8_t* out, i
   return L;
 }
 
+void Engine::launch_rows(size_t pi, PassLaunch L, Rows r, hipStream_t s) {
+  L.nrange = r.n;
+  std::copy(r.y, r.y + 4, L.ry);
+  launch_pass(plan_.passes[pi], prt_[pi].pc, L, s);
+}
+
+void Engine::run_rows(size_t pi, const uint8_t* in, uint8_t* out, Rows r, hipStream_t s, int ext, const uint8_t* in2,
+                      const Pass* resolved) {
+  if (device()) {
+    PassLaunch L = make_launch(pi, in, out, in2);
+    L.ext = ext;
+    launch_rows(pi, L, r, s);
+    return;
+  }
+  STRIPE_CHECK(r.n == 1, "a host pass takes one row range, got " << r.n);
+  const Pass& p = resolved ? *resolved : plan_.passes[pi];
+  cpu_pass(p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, geom(), r.y[0], r.y[1], host_threads(),
+           ConstView{in2, pitch(p.cin)});
+}
+
 int Engine::free_buf() const {
   if (!buf_[2].data()) return cur_ ^ 1;
   for (int i = 0; i < 3; ++i)
@@ -730,7 +751,8 @@ void Engine::apply_slots(const Pass& p) {
   }
 }
 
-void Engine::step_pass(const Pass& p) {
+void Engine::step_pass(size_t pi) {
+  const Pass& p = plan_.passes[pi];
   apply_slots(p);
   const int o = free_buf();
   const uint8_t* in2 = nullptr;
@@ -738,13 +760,13 @@ void Engine::step_pass(const Pass& p) {
     STRIPE_CHECK(held_ >= 0, "combine pass with nothing held" << (cfg_.held_input ? " (load_held_packed first)" : ""));
     in2 = origin(buf_[held_], p.cin);
   }
-  run_pass(p, origin(buf_[cur_], p.cin), origin(buf_[o], p.cout), in2);
+  run_pass(pi, origin(buf_[cur_], p.cin), origin(buf_[o], p.cout), in2);
   cur_ = o;
 }
 
-void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint8_t* in2) {
-  const Stripe& st = stripe();
-  const int rows = st.rows;
+void Engine::run_pass(size_t pi, const uint8_t* in, uint8_t* out, const uint8_t* in2) {
+  const Pass& p = plan_.passes[pi];
+  const int rows = stripe().rows;
   if (rows == 0) return;
   if (p.fill_in && device()) {
     // branched plans: the stencil writes its input's x-margins itself, before
@@ -757,8 +779,7 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint
   // a statistic op: the table of this pass's input over all active ranks, in
   // the pass's LUT block (device) / in the resolved pass (host)
   Pass resolved;
-  if (p.data_dependent()) resolved = prepare_stat(p, in, (int)(&p - plan_.passes.data()));
-  const RowGeom g = geom();
+  if (p.data_dependent()) resolved = prepare_stat(p, in, (int)pi);
   const int R = p.R;
   const bool xchg = !halo_done_ && ((cfg_.halo && R > 0 && neighbours()) || (device() && schedule_emu() == 1 && R > 0));
   // sends of a serial exchange complete lazily (Comm::hint_lazy_sends): any
@@ -767,35 +788,12 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint
   const bool serial_xchg = device() && xchg && !(cfg_.overlap && rows > 2 * R) && schedule_emu() != 3;
   if (!serial_xchg && comm_) comm_->flush_sends();
   if (device() && schedule_emu() == 3 && R > 0 && rows > 2 * R) {  // two launches, one stream, no events
-    const size_t pi3 = (size_t)(&p - plan_.passes.data());
-    PassLaunch L3 = make_launch(p, in, out, (int)pi3);
-    L3.nrange = 1;
-    L3.ry[0] = R;
-    L3.ry[1] = rows - R;
-    launch_pass(p, prt_[pi3].pc, L3, s_compute_);
-    L3.nrange = 2;
-    L3.ry[0] = 0;
-    L3.ry[1] = R;
-    L3.ry[2] = rows - R;
-    L3.ry[3] = rows;
-    launch_pass(p, prt_[pi3].pc, L3, s_compute_);
+    const PassLaunch L = make_launch(pi, in, out);
+    launch_rows(pi, L, {R, rows - R}, s_compute_);
+    launch_rows(pi, L, {0, R, rows - R, rows}, s_compute_);
     return;
   }
-  if (!device()) {
-    if (xchg) exchange_halo(const_cast<uint8_t*>(in), p.cin, R, nullptr);
-    cpu_pass(p.data_dependent() ? resolved : p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, g, 0,
-             rows, host_threads(), ConstView{in2, pitch(p.cin)});
-    return;
-  }
-  const size_t pi = (size_t)(&p - plan_.passes.data());
-  const PassConsts& pc = prt_[pi].pc;
-  PassLaunch L = make_launch(p, in, out, (int)pi, in2);
-  if (!xchg) {
-    L.nrange = 1;
-    L.ry[0] = 0;
-    L.ry[1] = rows;
-    launch_pass(p, pc, L, s_compute_);
-  } else if (cfg_.overlap && rows > 2 * R) {
+  if (device() && xchg && cfg_.overlap && rows > 2 * R) {
     // halo rows fly on the comm stream while the interior rows are computed;
     // the boundary rows follow their halo on the comm stream, beside the
     // interior launch, and the compute stream joins at the end (with the
@@ -806,40 +804,32 @@ void Engine::run_pass(const Pass& p, const uint8_t* in, uint8_t* out, const uint
       const char* e = std::getenv("STRIPE_OVERLAP_EDGES");
       return !(e && std::strcmp(e, "compute") == 0);
     }();
+    const PassLaunch L = make_launch(pi, in, out, in2);
+    const Rows edges{0, R, rows - R, rows};
     HIP_CHECK(hipEventRecord(ev_[4], s_compute_));
     HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_[4], 0));
     exchange_halo(const_cast<uint8_t*>(in), p.cin, R, s_comm_);
-    PassLaunch E = L;
-    E.nrange = 2;
-    E.ry[0] = 0;
-    E.ry[1] = R;
-    E.ry[2] = rows - R;
-    E.ry[3] = rows;
-    if (edges_on_comm) launch_pass(p, pc, E, s_comm_);
+    if (edges_on_comm) launch_rows(pi, L, edges, s_comm_);
     HIP_CHECK(hipEventRecord(ev_[5], s_comm_));
-    L.nrange = 1;
-    L.ry[0] = R;
-    L.ry[1] = rows - R;
-    launch_pass(p, pc, L, s_compute_);
+    launch_rows(pi, L, {R, rows - R}, s_compute_);
     HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_[5], 0));
-    if (!edges_on_comm) launch_pass(p, pc, E, s_compute_);
-  } else {
-    // the rows sent here are next written by the pass after this one, whose
-    // own exchange comes first on this stream (or run()'s flush_sends)
-    exchange_halo(const_cast<uint8_t*>(in), p.cin, R, s_compute_, lazy_sends_ok());
-    L.nrange = 1;
-    L.ry[0] = 0;
-    L.ry[1] = rows;
-    launch_pass(p, pc, L, s_compute_);
+    if (!edges_on_comm) launch_rows(pi, L, edges, s_compute_);
+    return;
   }
+  // the rows a serial device exchange sends are next written by the pass after
+  // this one, whose own exchange comes first on this stream (or run()'s
+  // flush_sends): its sends may complete lazily
+  if (xchg) exchange_halo(const_cast<uint8_t*>(in), p.cin, R, s_compute_, device() && lazy_sends_ok());
+  run_rows(pi, in, out, {0, rows}, s_compute_, 0, in2, p.data_dependent() ? &resolved : nullptr);
 }
 
 // Graph replay is safe when run() issues no collective: one active rank, or a
 // chain without halo exchange.  (RCCL calls are kept out of captured graphs.)
 bool Engine::graph_ok() const {
   if (!device() || !cfg_.graphs) return false;
-  if (plan_.data_dependent()) return false;  // a statistic pass synchronises and may reduce over the ranks
-  if (plan_.branched()) return false;        // three buffers: the two-buffer replay cycle does not hold
+  // a statistic pass synchronises and may reduce over the ranks; with three
+  // buffers the two-buffer replay cycle does not hold
+  if (!plan_.static_chain()) return false;
   const bool comm = cfg_.halo && plan_.max_radius > 0 && neighbours();
   return !comm && stripe().rows > 0;
 }
@@ -861,7 +851,7 @@ void Engine::run(int iterations) {
       time_halo_ = it == n - 1;  // two event records per exchange: only where they are read
       STRIPE_CHECK(cur_c_ == plan_.cin, "engine input has " << cur_c_ << " channels, chain expects " << plan_.cin);
       reset_held();  // the held slot is empty (or holds the external image) as an iteration starts
-      for (const Pass& p : plan_.passes) step_pass(p);
+      for (size_t pi = 0; pi < plan_.passes.size(); ++pi) step_pass(pi);
       cur_c_ = plan_.cout;
     }
   };

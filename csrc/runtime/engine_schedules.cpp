@@ -35,19 +35,16 @@ namespace stripe {
 // core/rim events alternate by step parity so core_k never waits rim_k.
 // ---------------------------------------------------------------------------
 bool Engine::pipelined_ok() const {
-  if (plan_.data_dependent()) return false;  // statistic passes take the plain per-pass path
-  if (plan_.branched()) return false;        // so do chains with a held image (three buffers)
-  if (device() && schedule_emu() == 2 && plan_.passes.size() == 1 && plan_.cin == plan_.cout &&
-      stripe().rows > 4 * plan_.passes[0].R && plan_.passes[0].R > 0)
-    return true;
+  // statistic passes and chains with a held image (three buffers) take the plain per-pass path
+  if (!one_static_pass() || plan_.cin != plan_.cout) return false;
+  const int R = plan_.passes[0].R, rows = stripe().rows;
+  if (R <= 0 || rows <= 4 * R) return false;
+  if (device() && schedule_emu() == 2) return true;
   if (!device() || !cfg_.halo || !cfg_.overlap || !neighbours()) return false;
-  if (plan_.passes.size() != 1 || plan_.cin != plan_.cout) return false;
-  const int R = plan_.passes[0].R;
   // large windows (MFMA blur) pay a whole 32-row group per thin rim range:
   // the three-way split costs more than it hides (blur:31 stripe 0.124 vs 0.114 ms)
-  if (plan_.passes[0].kind == PassKind::Conv && schedule_emu() != 2) return false;
-  const int rows = stripe().rows;
-  return R > 0 && rows > 4 * R && comm_ != nullptr;
+  if (plan_.passes[0].kind == PassKind::Conv) return false;
+  return comm_ != nullptr;
 }
 
 void Engine::set_halo_schedule(int s) {
@@ -81,19 +78,15 @@ void Engine::run_pipelined(int iterations) {
   HIP_CHECK(hipStreamWaitEvent(s_edge_, ev_start, 0));
   HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_start, 0));
   for (hipEvent_t e : {ev_core[1], ev_rim[1], ev_bnd}) HIP_CHECK(hipEventRecord(e, s_compute_));
-  const PassConsts& pc = prt_[0].pc;
   for (int k = 0; k < iterations; ++k) {
     time_halo_ = k == iterations - 1;
     const int par = k & 1;
     uint8_t* in = origin(buf_[cur_], p.cin);
     uint8_t* out = origin(buf_[cur_ ^ 1], p.cout);
-    PassLaunch L = make_launch(p, in, out, 0);
+    const PassLaunch L = make_launch(0, in, out);
     // core (main stream)
     HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_rim[par ^ 1], 0));
-    L.nrange = 1;
-    L.ry[0] = 2 * R;
-    L.ry[1] = rows - 2 * R;
-    launch_pass(p, pc, L, s_compute_);
+    launch_rows(0, L, {2 * R, rows - 2 * R}, s_compute_);
     HIP_CHECK(hipEventRecord(ev_core[par], s_compute_));
     // halo exchange (comm stream) once the previous boundary rows exist
     HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_bnd, 0));
@@ -101,20 +94,11 @@ void Engine::run_pipelined(int iterations) {
     HIP_CHECK(hipEventRecord(ev_x, s_comm_));
     // rim (edge stream)
     HIP_CHECK(hipStreamWaitEvent(s_edge_, ev_core[par ^ 1], 0));
-    L.nrange = 2;
-    L.ry[0] = R;
-    L.ry[1] = 2 * R;
-    L.ry[2] = rows - 2 * R;
-    L.ry[3] = rows - R;
-    launch_pass(p, pc, L, s_edge_);
+    launch_rows(0, L, {R, 2 * R, rows - 2 * R, rows - R}, s_edge_);
     HIP_CHECK(hipEventRecord(ev_rim[par], s_edge_));
     // boundary rows (edge stream) after the halo arrived
     HIP_CHECK(hipStreamWaitEvent(s_edge_, ev_x, 0));
-    L.ry[0] = 0;
-    L.ry[1] = R;
-    L.ry[2] = rows - R;
-    L.ry[3] = rows;
-    launch_pass(p, pc, L, s_edge_);
+    launch_rows(0, L, {0, R, rows - R, rows}, s_edge_);
     HIP_CHECK(hipEventRecord(ev_bnd, s_edge_));
     cur_ ^= 1;
     cur_c_ = plan_.cout;
@@ -143,10 +127,9 @@ void Engine::run_pipelined(int iterations) {
 // ---------------------------------------------------------------------------
 int Engine::chain_reach() const {
   // a statistic pass needs the histogram of its whole input before it runs: no
-  // deep halo, no deep steps (the recomputed neighbour rows would need it too)
-  if (plan_.data_dependent()) return 0;
+  // deep halo, no deep steps (the recomputed neighbour rows would need it too);
   // a held image: the deep schedules walk a static two-buffer chain
-  if (plan_.branched()) return 0;
+  if (!plan_.static_chain()) return 0;
   int s = 0;
   for (const Pass& p : plan_.passes) {
     if (p.kind != PassKind::Pointwise && p.kind != PassKind::Separable && p.kind != PassKind::Direct) return 0;
@@ -184,9 +167,7 @@ int Engine::choose_depth() const {
 void Engine::run_deep(int iterations) {
   const int S = chain_reach(), rows = stripe().rows;
   if (rows == 0) return;
-  const bool up = has_up(), down = has_down();
   const Pass& p0 = plan_.passes[0];
-  const int R0 = p0.R;
   // the block's exchange flies on the comm stream beside the first pass's
   // interior rows [R0, rows - R0), which read only the rank's own rows; its
   // boundary rows follow once the halo has landed (two cross-stream waits per
@@ -195,8 +176,7 @@ void Engine::run_deep(int iterations) {
     const char* e = std::getenv("STRIPE_DEEP_OVERLAP");
     return !e || std::atoi(e) != 0;
   }();
-  const bool overlap = device() && cfg_.overlap && env_overlap && rows > 2 * R0;
-  const int iy0 = up ? R0 : 0, iy1 = down ? rows - R0 : rows;  // rows needing no halo
+  const bool overlap = device() && cfg_.overlap && env_overlap && rows > 2 * p0.R;
   for (int done = 0; done < iterations;) {
     const int m = std::min(depth_, iterations - done);
     time_halo_ = done + m >= iterations;  // stage events of the last exchange only
@@ -208,45 +188,39 @@ void Engine::run_deep(int iterations) {
     } else {
       exchange_halo(origin(buf_[cur_], p0.cin), p0.cin, m * S, s_compute_);
     }
-    for (int i = 0; i < m; ++i) {
-      int reach = (m - i) * S;  // halo rows valid in the current input
-      for (size_t k = 0; k < plan_.passes.size(); ++k) {
-        const Pass& p = plan_.passes[k];
-        reach -= p.R;  // halo rows this pass's output must cover
-        const int y0 = up ? -reach : 0, y1 = rows + (down ? reach : 0);
-        uint8_t* in = origin(buf_[cur_], p.cin);
-        uint8_t* out = origin(buf_[cur_ ^ 1], p.cout);
-        if (device()) {
-          PassLaunch L = make_launch(p, in, out, (int)k);
-          L.ext = reach;
-          if (overlap && i == 0 && k == 0) {
-            L.nrange = 1;
-            L.ry[0] = iy0;
-            L.ry[1] = iy1;
-            launch_pass(p, prt_[k].pc, L, s_compute_);
-            HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_[5], 0));
-            L.nrange = 2;
-            L.ry[0] = y0;
-            L.ry[1] = iy0;
-            L.ry[2] = iy1;
-            L.ry[3] = y1;
-          } else {
-            L.nrange = 1;
-            L.ry[0] = y0;
-            L.ry[1] = y1;
-          }
-          launch_pass(p, prt_[k].pc, L, s_compute_);
-        } else {
-          cpu_pass(p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, geom(), y0, y1,
-                   host_threads());
-        }
-        cur_ ^= 1;
-      }
-    }
+    for (int i = 0; i < m; ++i) deep_block_step(m, i, overlap && i == 0);
     done += m;
   }
   cur_c_ = plan_.cout;
   time_halo_ = true;
+}
+
+// The passes of step i of an m-step deep block, whose exchange brought m * S
+// rows of each neighbour: every pass computes the stripe plus the band of
+// neighbour rows the rest of the block still reads.
+void Engine::deep_block_step(int m, int i, bool overlap_first) {
+  const int rows = stripe().rows;
+  const bool up = has_up(), down = has_down();
+  int reach = (m - i) * chain_reach();  // halo rows valid in the current input
+  for (size_t k = 0; k < plan_.passes.size(); ++k) {
+    const Pass& p = plan_.passes[k];
+    reach -= p.R;  // halo rows this pass's output must cover
+    const int y0 = up ? -reach : 0, y1 = rows + (down ? reach : 0);
+    const uint8_t* in = origin(buf_[cur_], p.cin);
+    uint8_t* out = origin(buf_[cur_ ^ 1], p.cout);
+    if (overlap_first && k == 0) {
+      // the rows needing no halo beside the exchange, the two outer ranges once it has landed
+      const int iy0 = up ? p.R : 0, iy1 = down ? rows - p.R : rows;
+      PassLaunch L = make_launch(k, in, out);
+      L.ext = reach;
+      launch_rows(k, L, {iy0, iy1}, s_compute_);
+      HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_[5], 0));
+      launch_rows(k, L, {y0, iy0, iy1, y1}, s_compute_);
+    } else {
+      run_rows(k, in, out, {y0, y1}, s_compute_, reach);
+    }
+    cur_ ^= 1;
+  }
 }
 
 void Engine::set_deep_steps(bool on) {
@@ -259,38 +233,17 @@ bool Engine::deep_stepping() const {
   return deep_steps_ && depth_ > 1 && plan_.cin == plan_.cout && chain_reach() > 0;
 }
 
-// One step of a deep-halo block (set_deep_steps): run_deep's loop body for
-// step deep_phase_ of a depth_-step block, so callers can interleave other work
-// (a frame stream's other frames) between the steps.  The block's first step
-// exchanges depth_ * S rows (unless run_posted's group already did); step i
-// then computes its passes over the stripe plus (depth_ - i) * S - R rows of
-// each neighbour, rows every later step of the block reads.
+// One step of a deep-halo block (set_deep_steps): step deep_phase_ of a
+// depth_-step block on its own, so callers can interleave other work (a frame
+// stream's other frames) between the steps.  The block's first step exchanges
+// depth_ * S rows (unless run_posted's group already did).
 void Engine::deep_step() {
-  const int S = chain_reach(), rows = stripe().rows, m = depth_, i = deep_phase_;
+  const int m = depth_, i = deep_phase_;
   deep_phase_ = (i + 1) % m;
-  if (rows == 0) return;
-  const bool up = has_up(), down = has_down();
+  if (stripe().rows == 0) return;
   const Pass& p0 = plan_.passes[0];
-  if (i == 0 && !halo_done_) exchange_halo(origin(buf_[cur_], p0.cin), p0.cin, m * S, s_compute_);
-  int reach = (m - i) * S;  // halo rows valid in the current input
-  for (size_t k = 0; k < plan_.passes.size(); ++k) {
-    const Pass& p = plan_.passes[k];
-    reach -= p.R;  // halo rows this pass's output must cover
-    const int y0 = up ? -reach : 0, y1 = rows + (down ? reach : 0);
-    uint8_t* in = origin(buf_[cur_], p.cin);
-    uint8_t* out = origin(buf_[cur_ ^ 1], p.cout);
-    if (device()) {
-      PassLaunch L = make_launch(p, in, out, (int)k);
-      L.ext = reach;
-      L.nrange = 1;
-      L.ry[0] = y0;
-      L.ry[1] = y1;
-      launch_pass(p, prt_[k].pc, L, s_compute_);
-    } else {
-      cpu_pass(p, ConstView{in, pitch(p.cin)}, MutView{out, pitch(p.cout)}, cfg_.W, geom(), y0, y1, host_threads());
-    }
-    cur_ ^= 1;
-  }
+  if (i == 0 && !halo_done_) exchange_halo(origin(buf_[cur_], p0.cin), p0.cin, m * chain_reach(), s_compute_);
+  deep_block_step(m, i);
 }
 
 }  // namespace stripe

@@ -48,6 +48,16 @@ E2EMode e2e_mode() {
 }
 }  // namespace
 
+// The per-chunk upload and compute events of run_e2e / run_to_host grow together.
+void Engine::ensure_chunk_events(int n) {
+  while ((int)ev_cmp_.size() < n)
+    for (auto* v : {&ev_h2d_, &ev_cmp_}) {
+      hipEvent_t e;
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      v->push_back(e);
+    }
+}
+
 void Engine::run_e2e(int chunks) {
   STRIPE_CHECK(device(), "run_e2e needs the device backend");
   STRIPE_CHECK(host_in_.data() && host_out_.data(), "call alloc_host_io() first");
@@ -62,13 +72,7 @@ void Engine::run_e2e(int chunks) {
     HIP_CHECK(hipStreamCreateWithFlags(&s_d2h_, hipStreamNonBlocking));
   }
   chunks = std::max(1, std::min(chunks, rows));
-  while ((int)ev_h2d_.size() < chunks + 1) {
-    hipEvent_t e1, e2;
-    HIP_CHECK(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-    ev_h2d_.push_back(e1);
-    ev_cmp_.push_back(e2);
-  }
+  ensure_chunk_events(chunks + 1);
   const int cin = plan_.cin, cout = plan_.cout;
   const int64_t Ein = (int64_t)cfg_.W * cin, Eout = (int64_t)cfg_.W * cout;
   std::vector<int> cut(chunks + 1);
@@ -125,7 +129,7 @@ void Engine::run_e2e(int chunks) {
   }
   stage_end(Stage::H2D, s_h2d_);
   // (a statistic pass needs its whole input before it runs: unpipelined too)
-  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent() && !plan_.branched();
+  const bool single = one_static_pass();
   if (!single) {
     // multi-pass chains: upload overlapped with nothing but the download of the
     // previous step; the chain itself runs as usual
@@ -146,7 +150,7 @@ void Engine::run_e2e(int chunks) {
   const bool up = xchg && has_up();
   const bool down = xchg && has_down();
   uint8_t* out_org = origin(buf_[1], cout);
-  PassLaunch L = make_launch(p, in_org, out_org, 0);
+  const PassLaunch L = make_launch(0, in_org, out_org);
   if (xchg) {  // halo rows come from the first and last chunks
     HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_h2d_[0], 0));
     HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_h2d_[chunks - 1], 0));
@@ -163,10 +167,7 @@ void Engine::run_e2e(int chunks) {
     const int avail = i == chunks - 1 ? rows : std::max(0, cut[i + 1] - R);  // inputs loaded for y + R
     const int hi = std::min(avail, hi_lim);
     if (hi > done) {
-      L.nrange = 1;
-      L.ry[0] = done;
-      L.ry[1] = hi;
-      launch_pass(p, prt_[0].pc, L, s_compute_);
+      launch_rows(0, L, {done, hi}, s_compute_);
       ranges[i] = {done, hi};
       done = hi;
     }
@@ -177,18 +178,9 @@ void Engine::run_e2e(int chunks) {
   }
   if (xchg) {  // boundary rows once the neighbours' halos are in
     HIP_CHECK(hipStreamWaitEvent(s_compute_, ev_[5], 0));
-    L.nrange = 0;
-    if (up) {
-      L.ry[2 * L.nrange] = 0;
-      L.ry[2 * L.nrange + 1] = lo_lim;
-      ++L.nrange;
-    }
-    if (down) {
-      L.ry[2 * L.nrange] = hi_lim;
-      L.ry[2 * L.nrange + 1] = rows;
-      ++L.nrange;
-    }
-    if (L.nrange > 0) launch_pass(p, prt_[0].pc, L, s_compute_);
+    if (up && down) launch_rows(0, L, {0, lo_lim, hi_lim, rows}, s_compute_);
+    else if (up) launch_rows(0, L, {0, lo_lim}, s_compute_);
+    else if (down) launch_rows(0, L, {hi_lim, rows}, s_compute_);
     HIP_CHECK(hipEventRecord(ev_cmp_[chunks], s_compute_));
     HIP_CHECK(hipStreamWaitEvent(s_d2h_, ev_cmp_[chunks], 0));
     if (up) download(out_org, 0, lo_lim);
@@ -231,9 +223,9 @@ void Engine::join_d2h() {
 // y - R .. y + R); anything else runs the three calls.
 // ---------------------------------------------------------------------------
 int Engine::dist_chunks(int chunks) const {
-  if (!comm_ || part_.active <= 1 || chunks < 2 || plan_.passes.size() != 1) return 0;
-  if (plan_.data_dependent()) return 0;  // the table needs the whole frame: scatter, run, gather
-  if (plan_.branched()) return 0;        // a held image: scatter, run, gather
+  if (!comm_ || part_.active <= 1 || chunks < 2) return 0;
+  // (a statistic table needs the whole frame, a held image three buffers: scatter, run, gather)
+  if (!one_static_pass()) return 0;
   const Pass& p = plan_.passes[0];
   if (p.kind != PassKind::Separable && p.kind != PassKind::Direct && p.kind != PassKind::Pointwise) return 0;
   if (cfg_.halo && p.R > halo_) return 0;
@@ -244,10 +236,10 @@ int Engine::dist_chunks(int chunks) const {
 }
 
 bool Engine::dist_direct() const {
-  if (!device() || part_.active != 1 || rank_ != 0 || plan_.passes.size() != 1) return false;
+  if (!device() || part_.active != 1 || rank_ != 0) return false;
   if (!root_in_.data() || !root_out_.data()) return false;
-  if (plan_.data_dependent()) return false;  // prepare_stat reads the stripe buffers
-  if (plan_.branched()) return false;        // the held image lives in the stripe buffers
+  // (prepare_stat reads the stripe buffers, and a held image lives in them)
+  if (!one_static_pass()) return false;
   const Pass& p = plan_.passes[0];
   return p.kind == PassKind::Separable || p.kind == PassKind::Direct || p.kind == PassKind::Pointwise;
 }
@@ -259,15 +251,10 @@ void Engine::run_dist(int chunks) {
     // input and writes the root output directly (scatter and gather would be
     // two whole-frame device copies); the stripe buffers keep no output
     if (cfg_.autotune && !tuned_) autotune_bands();
-    const Pass& p = plan_.passes[0];
     TraceRange tr("stripe.dist");
     fault_point("scatter", rank_);
     stage_begin(Stage::Compute, s_compute_);
-    PassLaunch L = make_launch(p, root_origin(root_in_, plan_.cin), root_origin(root_out_, plan_.cout), 0);
-    L.nrange = 1;
-    L.ry[0] = 0;
-    L.ry[1] = L.rows;
-    launch_pass(p, prt_[0].pc, L, s_compute_);
+    run_rows(0, root_origin(root_in_, plan_.cin), root_origin(root_out_, plan_.cout), {0, stripe().rows}, s_compute_);
     stage_end(Stage::Compute, s_compute_);
     out_buf_ = -1;
     out_c_ = plan_.cout;
@@ -336,30 +323,9 @@ void Engine::run_dist(int chunks) {
   // the root's own share: root input -> root output in place (its local rows
   // are the frame's rows 0 .. rows - 1, so the root buffers are its stripe)
   auto compute_root = [&]() {
-    const uint8_t* ri = root_origin(root_in_, cin);
-    uint8_t* ro = root_origin(root_out_, cout);
-    if (dev) {
-      PassLaunch L = make_launch(p, ri, ro, 0);
-      L.nrange = 1;
-      L.ry[0] = 0;
-      L.ry[1] = st.rows;
-      launch_pass(p, prt_[0].pc, L, s_compute_);
-    } else {
-      cpu_pass(p, ConstView{ri, Pin}, MutView{ro, Pout}, cfg_.W, geom(), 0, st.rows, host_threads());
-    }
+    run_rows(0, root_origin(root_in_, cin), root_origin(root_out_, cout), {0, st.rows}, s_compute_);
   };
-  auto compute = [&](int k) {
-    const int y0 = cut(rank_, k), y1 = cut(rank_, k + 1);
-    if (dev) {
-      PassLaunch L = make_launch(p, in_org, out_org, 0);
-      L.nrange = 1;
-      L.ry[0] = y0;
-      L.ry[1] = y1;
-      launch_pass(p, prt_[0].pc, L, s_compute_);
-    } else {
-      cpu_pass(p, ConstView{in_org, Pin}, MutView{out_org, Pout}, cfg_.W, geom(), y0, y1, host_threads());
-    }
-  };
+  auto compute = [&](int k) { run_rows(0, in_org, out_org, {cut(rank_, k), cut(rank_, k + 1)}, s_compute_); };
   if (dev) {
     while ((int)dist_ev_.size() < 2 * n + 1) {
       hipEvent_t e;
@@ -458,13 +424,7 @@ void Engine::run_to_host(void* dst, int chunks) {
   TraceRange tr("stripe.to_host");
   if (!s_d2h_) HIP_CHECK(hipStreamCreateWithFlags(&s_d2h_, hipStreamNonBlocking));
   chunks = std::max(1, std::min(chunks, rows));
-  while ((int)ev_cmp_.size() < chunks + 1) {
-    hipEvent_t e1, e2;
-    HIP_CHECK(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-    ev_h2d_.push_back(e1);
-    ev_cmp_.push_back(e2);
-  }
+  ensure_chunk_events(chunks + 1);
   const int cout = plan_.cout;
   const int64_t Eout = (int64_t)cfg_.W * cout;
   uint8_t* host = static_cast<uint8_t*>(dst);
@@ -475,7 +435,7 @@ void Engine::run_to_host(void* dst, int chunks) {
   stage_begin(Stage::E2E, s_compute_);
   const Pass& p0 = plan_.passes[0];
   // any kind: launch_pass takes row ranges (a statistic pass goes through run())
-  const bool single = plan_.passes.size() == 1 && !plan_.data_dependent() && !plan_.branched();
+  const bool single = one_static_pass();
   if (!single) {  // multi-pass chains: the chain, then the download
     run(1);
     const int ob = out_buf_;
@@ -489,13 +449,10 @@ void Engine::run_to_host(void* dst, int chunks) {
     uint8_t* in = origin(buf_[in_buf], p0.cin);
     uint8_t* out = origin(buf_[in_buf ^ 1], cout);
     if (xchg) exchange_halo(in, p0.cin, p0.R, s_compute_);
-    PassLaunch L = make_launch(p0, in, out, 0);
+    const PassLaunch L = make_launch(0, in, out);
     for (int i = 0; i < chunks; ++i) {
       const int y0 = (int)((int64_t)rows * i / chunks), y1 = (int)((int64_t)rows * (i + 1) / chunks);
-      L.nrange = 1;
-      L.ry[0] = y0;
-      L.ry[1] = y1;
-      launch_pass(p0, prt_[0].pc, L, s_compute_);
+      launch_rows(0, L, {y0, y1}, s_compute_);
       HIP_CHECK(hipEventRecord(ev_cmp_[i], s_compute_));
       HIP_CHECK(hipStreamWaitEvent(s_d2h_, ev_cmp_[i], 0));
       if (i == 0) stage_begin(Stage::D2H, s_d2h_);

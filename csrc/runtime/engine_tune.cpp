@@ -134,12 +134,11 @@ void Engine::autotune_bands() {
     // tune is reduced, so a collective inside them would deadlock)
     // (a branched plan: any buffer but the current one takes the scratch output;
     // its combine passes are not tuned, they launch with whatever the buffers hold)
-    PassLaunch L = make_launch(p, origin(buf_[cur_], p.cin), origin(buf_[cur_ == 0 ? 1 : 0], p.cout), (int)i);
-    L.ry[0] = 0;
-    L.ry[1] = L.rows;
+    PassLaunch L = make_launch(i, origin(buf_[cur_], p.cin), origin(buf_[cur_ == 0 ? 1 : 0], p.cout));
+    const Rows whole{0, L.rows};
     auto launch_one = [&]() {
       if (nrot == 0) {
-        launch_pass(p, prt_[i].pc, L, s_compute_);
+        launch_rows(i, L, whole, s_compute_);
         return;
       }
       hipStream_t ls = (s2 && (rot & 1)) ? s2 : s_compute_;
@@ -154,7 +153,7 @@ void Engine::autotune_bands() {
       R.out = bo.data() + (L.out - L.out_base);
       R.out_base = bo.data();
       R.out_bytes = (int64_t)bo.bytes();
-      launch_pass(p, prt_[i].pc, R, ls);
+      launch_rows(i, R, whole, ls);
     };
     // median over 5 timed bursts (each after an untimed one) of kBurst
     // back-to-back launches: the steady state of an iterated run, where one

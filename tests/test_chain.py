@@ -86,6 +86,15 @@ def test_unfused_plan(C):
     assert len(info["passes"]) == 3
 
 
+@pytest.mark.parametrize("chain,static", [("gaussian5,invert", True), ("equalize,gaussian5", False),
+                                          ("hold,gaussian5,absdiff", False), ("unsharp", False)])
+def test_static_chain(C, chain, static):
+    # the one predicate the engine's deep, pipelined, posted, graph and chunked steps ask
+    info = C.plan_info(chain, 3)
+    assert info["static_chain"] is static
+    assert info["static_chain"] == (not info["data_dependent"] and not info["branched"])
+
+
 def test_presets_exist():
     for name in ["ref-gpu", "ref-cpu", "config1-gray", "config4-gauss5", "config5-blur31"]:
         p = models.Pipeline.preset(name)
