@@ -19,7 +19,8 @@
 //                [--frames F] [--json out.json]     (F: stream of F frames, resident scope)
 //   stripe cmp   a.ppm b.ppm [--tol 0]
 //   stripe gen   --synthetic WxHxC --seed S --output x.ppm
-//   stripe convert --input a.jpg --output b.ppm [--quality 95] [--resize WxH[:mode]]
+//   stripe convert --input a.jpg --output b.ppm [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]
+//                  [--resize WxH[:mode]]
 //   stripe info  [--chain ...] [--channels C] [--format json]
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,7 @@
 #include "stripe/cpu_exec.h"
 #include "stripe/engine.h"
 #include "stripe/kernels.h"
+#include "stripe/orient.h"
 #include "stripe/resize.h"
 #include "stripe/trace.h"
 
@@ -292,6 +294,66 @@ std::string resize_input(const Args& a, Input* in, bool on_device, int device) {
   return ",\"resized_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "]";
 }
 
+// --orient OP|auto and --crop WxH+X+Y: the frame is oriented and cropped, in one
+// pass, before --resize and the chain: on the GPU (k_orient) for device
+// backends, on cpu_orient for the host backend.  `auto` is the Exif Orientation
+// of a JPEG file (none for any other format).
+Orient orient_of(const Args& a, const std::string& path) {
+  const std::string t = a.get("orient", "none");
+  if (t != "auto") return parse_orient(t);
+  const std::string bytes = read_file(path);
+  return orient_from_exif(jpeg_orientation(reinterpret_cast<const uint8_t*>(bytes.data()), bytes.size()));
+}
+
+Image orient_image(const Image& in, Orient op, const CropRect& crop, bool on_device, int device) {
+  if (!on_device) return cpu_orient(in, op, crop, cpu_threads());
+  HIP_CHECK(hipSetDevice(device));
+  const bool t = orient_t(op);
+  Image out(crop.empty() ? (t ? in.H : in.W) : crop.w, crop.empty() ? (t ? in.W : in.H) : crop.h, in.C, NoInit{});
+  uint8_t *ds = nullptr, *dd = nullptr;
+  try {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
+    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
+    orient_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), op, crop, nullptr);
+    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipFree(ds);
+    (void)hipFree(dd);
+    throw;
+  }
+  HIP_CHECK(hipFree(ds));
+  HIP_CHECK(hipFree(dd));
+  return out;
+}
+
+// the --crop window, checked against the oriented frame of a W x H source
+CropRect crop_of(const Args& a, Orient op, int W, int H) {
+  if (!a.has("crop")) return {};
+  const CropRect c = parse_crop_spec(a.get("crop"));
+  check_crop(c, orient_t(op) ? H : W, orient_t(op) ? W : H, a.get("crop"));
+  return c;
+}
+
+// Applies --orient / --crop to the loaded input (a JPEG's coefficients are
+// decoded to pixels first); returns the JSON members that record the stage, or "".
+std::string orient_input(const Args& a, Input* in, const std::string& path, bool on_device, int device) {
+  if (!a.has("orient") && !a.has("crop")) return "";
+  const Orient op = orient_of(a, path);
+  const int W0 = in->W, H0 = in->H;
+  const CropRect crop = crop_of(a, op, W0, H0);
+  if (in->coefs) {
+    in->img = jpeg_pixels(std::move(in->jpeg));
+    in->jpeg = JpegCoefs{};
+    in->coefs = false;
+  }
+  in->img = orient_image(in->img, op, crop, on_device, device);
+  in->W = in->img.W;
+  in->H = in->img.H;
+  return std::string(",\"oriented\":\"") + orient_name(op) + "\",\"cropped_from\":[" + std::to_string(W0) + "," +
+         std::to_string(H0) + "]";
+}
+
 // One rank of a multi-process job: `stripe run --backend rccl --world N --rank r
 // --rendezvous FILE [--device d]` (like the reference's `mpiexec -n N`, one
 // process per rank; only rank 0 reads the input and writes the output).
@@ -307,7 +369,8 @@ int cmd_run_rank(const Args& a) {
   if (rank == 0) {
     STRIPE_CHECK(a.has("input") && a.has("output"), "rank 0 needs --input and --output");
     in = read_input(a.get("input"), true);
-    resized = resize_input(a, &in, true, device);  // before the geometry is broadcast
+    resized = orient_input(a, &in, a.get("input"), true, device);  // before the geometry is broadcast
+    resized += resize_input(a, &in, true, device);
     cfg = config_from(a, in.W, in.H, in.C);
   } else {
     cfg = config_from(a, 1, 1, 3);  // geometry arrives with the metadata broadcast
@@ -347,7 +410,8 @@ int cmd_run(const Args& a) {
   const auto tr = std::chrono::steady_clock::now();
   Input in = read_input(a.get("input"), !host_run);
   const std::vector<int> rdevs = parse_int_list(a.get("devices"));
-  const std::string resized = resize_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]);
+  const std::string resized = orient_input(a, &in, a.get("input"), !host_run, rdevs.empty() ? 0 : rdevs[0]) +
+                              resize_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]);
   const double read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
   EngineConfig cfg = config_from(a, in.W, in.H, in.C);
   const int N = a.geti("ranks", 1);
@@ -363,6 +427,10 @@ int cmd_run(const Args& a) {
     // two-image form of the combine ops): one engine, no scatter / gather
     STRIPE_CHECK(N == 1, "--held is single-process only (--ranks 1), got --ranks " << N);
     Image held = read_image(a.get("held"));
+    if (a.has("orient") || a.has("crop")) {  // the held image is oriented and cropped the same way
+      const Orient hop = orient_of(a, a.get("held"));
+      held = orient_image(held, hop, crop_of(a, hop, held.W, held.H), !host_run, rdevs.empty() ? 0 : rdevs[0]);
+    }
     if (a.has("resize"))  // the held image is resized the same way
       held = resize_image(held, parse_resize_spec(a.get("resize")), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
@@ -447,7 +515,8 @@ int cmd_convert(const Args& a) {
   in.W = in.img.W, in.H = in.img.H, in.C = in.img.C;
   const bool host_run = a.get("backend", device_count() > 0 ? "local" : "host") == "host";
   const std::vector<int> devs = parse_int_list(a.get("devices"));
-  const std::string resized = resize_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]);
+  const std::string resized = orient_input(a, &in, a.get("input"), !host_run, devs.empty() ? 0 : devs[0]) +
+                              resize_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]);
   const Image& img = in.img;
   write_image(a.get("output"), img, a.geti("quality", 95));
   std::printf("{\"cmd\":\"convert\",\"W\":%d,\"H\":%d,\"C\":%d%s}\n", img.W, img.H, img.C, resized.c_str());
@@ -773,6 +842,9 @@ void usage() {
                "        [--expand-gray] [--legacy-partition] [--iterations K] [--no-fuse] [--no-overlap]\n"
                "        [--dist-chunks K]  (> 1 ranks, single-pass chains: pipelined scatter/filter/gather)\n"
                "        [--held other.ppm]  (a second image of equal size, held for add/sub/absdiff/blend:t/...; --ranks 1)\n"
+               "        [--orient none|fliph|rot180|flipv|transpose|rot90|transverse|rot270|exif:N|auto] [--crop WxH+X+Y]\n"
+               "            (the frame, and --held's, oriented and cropped before --resize and the chain; auto: the\n"
+               "             Exif Orientation of a JPEG input; --crop is a window of the oriented frame)\n"
                "        [--resize WxH[:auto|nearest|bilinear|area]]  (the frame, and --held's, resized before the chain)\n"
                "        one process per rank: --backend rccl --world N --rank r --rendezvous FILE [--device d]\n"
                "  bench --synthetic WxHxC [--seed S] [--chain C] [--ranks 1,2,4,8] [--iters N] [--warmup N]\n"
@@ -782,7 +854,8 @@ void usage() {
                "        [--halo-schedule auto|serial|overlap|pipeline|batched|serial+deep]  (frames at N > 1: auto times each)\n"
                "  cmp   a.ppm b.ppm [--tol T]\n"
                "  gen   --synthetic WxHxC [--seed S] --output out.ppm|out.jpg\n"
-               "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95] [--resize WxH[:mode]] [--backend host]\n"
+               "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]\n"
+               "        [--resize WxH[:mode]] [--backend host]\n"
                "  info  [--chain C] [--channels C] [--format json]\n");
 }
 

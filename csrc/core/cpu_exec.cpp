@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "stripe/orient.h"
 #include "stripe/rank_net.h"
 #include "stripe/resize.h"
 
@@ -630,6 +631,86 @@ Image cpu_resize(const Image& in, int W2, int H2, ResizeMode mode, int threads) 
                "resize: size " << W2 << "x" << H2 << " outside 1.." << kResizeMaxSize);
   Image out(W2, H2, in.C, NoInit{});
   cpu_resize(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), W2, H2, mode,
+             threads);
+  return out;
+}
+
+// ---- orientation and crop (stripe/orient.h) ----
+namespace {
+// one output row of a non-transposing op: a copy, or the row's pixels in reverse order
+template <int C>
+void orient_row(const uint8_t* __restrict s, uint8_t* __restrict d, int w, bool fx) {
+  if (!fx) {
+    std::memcpy(d, s, (size_t)w * C);
+    return;
+  }
+  const uint8_t* p = s + (size_t)(w - 1) * C;
+  for (int x = 0; x < w; ++x, p -= C, d += C)
+    for (int c = 0; c < C; ++c) d[c] = p[c];
+}
+
+// output rows [ya, yb) of a transposing op, tile by tile: within a tile the
+// source is read along its rows and the destination written down a column of
+// at most kCpuOrientTile rows, both of which stay in the cache
+template <int C>
+void orient_transposed(const uint8_t* src, int64_t sp, int w, int h, uint8_t* dst, int64_t dp, bool fx, bool fy, int ya,
+                       int yb) {
+  constexpr int TS = kCpuOrientTile;
+  for (int y0 = ya; y0 < yb; y0 += TS) {
+    const int y1 = std::min(y0 + TS, yb);
+    for (int x0 = 0; x0 < h; x0 += TS) {  // the output is h pixels wide
+      const int x1 = std::min(x0 + TS, h);
+      for (int x = x0; x < x1; ++x) {
+        const uint8_t* srow = src + (int64_t)(fy ? h - 1 - x : x) * sp;
+        uint8_t* d = dst + (int64_t)y0 * dp + (size_t)x * C;
+        if (!fx) {
+          const uint8_t* p = srow + (size_t)y0 * C;
+          for (int y = y0; y < y1; ++y, p += C, d += dp)
+            for (int c = 0; c < C; ++c) d[c] = p[c];
+        } else {
+          const uint8_t* p = srow + (size_t)(w - 1 - y0) * C;
+          for (int y = y0; y < y1; ++y, p -= C, d += dp)
+            for (int c = 0; c < C; ++c) d[c] = p[c];
+        }
+      }
+    }
+  }
+}
+}  // namespace
+
+void cpu_orient(const uint8_t* src, int64_t src_pitch, int w, int h, int C, uint8_t* dst, int64_t dst_pitch, Orient op,
+                int threads) {
+  STRIPE_CHECK(C == 1 || C == 3, "orient: image must have 1 or 3 channels, got C = " << C);
+  STRIPE_CHECK(src && dst && w >= 1 && h >= 1, "orient: empty image");
+  const bool t = orient_t(op), fx = orient_fx(op), fy = orient_fy(op);
+  const int W2 = t ? h : w, H2 = t ? w : h;
+  STRIPE_CHECK(src_pitch >= (int64_t)w * C && dst_pitch >= (int64_t)W2 * C, "orient: pitch smaller than a row");
+  parallel_rows(0, H2, 2 * (int64_t)W2 * C, std::max(1, threads), [&](int ya, int yb) {
+    if (!t) {
+      for (int y = ya; y < yb; ++y) {
+        const uint8_t* s = src + (int64_t)(fy ? h - 1 - y : y) * src_pitch;
+        if (C == 1) orient_row<1>(s, dst + (int64_t)y * dst_pitch, w, fx);
+        else orient_row<3>(s, dst + (int64_t)y * dst_pitch, w, fx);
+      }
+    } else if (C == 1) {
+      orient_transposed<1>(src, src_pitch, w, h, dst, dst_pitch, fx, fy, ya, yb);
+    } else {
+      orient_transposed<3>(src, src_pitch, w, h, dst, dst_pitch, fx, fy, ya, yb);
+    }
+  });
+}
+
+Image cpu_orient(const Image& in, Orient op, const CropRect& crop, int threads) {
+  STRIPE_CHECK(in.C == 1 || in.C == 3, "orient: image must have 1 or 3 channels, got C = " << in.C);
+  STRIPE_CHECK(in.W >= 1 && in.H >= 1 && in.W <= kOrientMaxSize && in.H <= kOrientMaxSize,
+               "orient: size " << in.W << "x" << in.H << " outside 1.." << kOrientMaxSize);
+  if (!crop.empty())
+    check_crop(crop, orient_t(op) ? in.H : in.W, orient_t(op) ? in.W : in.H,
+               std::to_string(crop.w) + "x" + std::to_string(crop.h) + "+" + std::to_string(crop.x0) + "+" +
+                   std::to_string(crop.y0));
+  const CropRect s = orient_source_window(op, in.W, in.H, crop);
+  Image out(orient_t(op) ? s.h : s.w, orient_t(op) ? s.w : s.h, in.C, NoInit{});
+  cpu_orient(in.row(s.y0) + (size_t)s.x0 * in.C, in.row_bytes(), s.w, s.h, in.C, out.data.data(), out.row_bytes(), op,
              threads);
   return out;
 }

@@ -134,6 +134,30 @@ void launch_resize(const ResizeLaunch& L, hipStream_t s) {
   launch_resize_kernel(L, s);
 }
 
+void launch_orient(const OrientLaunch& L, hipStream_t s) {
+  // host-side shape checks before the kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad orient launch: null src or dst");
+  STRIPE_CHECK(L.C == 1 || L.C == 3, "orient needs 1 or 3 channels, got C = " << L.C);
+  STRIPE_CHECK(L.w >= 1 && L.w <= kOrientMaxSize && L.h >= 1 && L.h <= kOrientMaxSize,
+               "orient: source size " << L.w << "x" << L.h << " outside 1.." << kOrientMaxSize);
+  STRIPE_CHECK((int)L.op >= 0 && (int)L.op < 8, "orient: bad orientation " << (int)L.op);
+  const int W2 = orient_t(L.op) ? L.h : L.w, H2 = orient_t(L.op) ? L.w : L.h;
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.w * L.C, "orient: src_pitch " << L.src_pitch << " < row bytes " << L.w * L.C);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)W2 * L.C, "orient: dst_pitch " << L.dst_pitch << " < row bytes " << W2 * L.C);
+  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
+  // Where the caller names the allocations, the rows touched lie inside them.
+  if (L.src_base)
+    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.h - 1) * L.src_pitch + (int64_t)L.w * L.C <=
+                                            L.src_bytes,
+                 "orient: source rows outside their buffer");
+  if (L.dst_base)
+    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(H2 - 1) * L.dst_pitch + (int64_t)W2 * L.C <=
+                                            L.dst_bytes,
+                 "orient: destination rows outside their buffer");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_orient_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

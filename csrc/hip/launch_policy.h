@@ -179,6 +179,7 @@ enum class Family {
   Blur,           // k_blur_pl
   Combine,        // k_combine
   Resize,         // k_resize
+  Orient,         // k_orient
 };
 
 struct PolicyIn {
@@ -227,7 +228,7 @@ constexpr int stencil_cap_default(Family f, bool gray_prologue) {
 //   * all pointwise families and k_conv_small ignore PassLaunch::nt;
 //   * channel-changing pointwise applies its cap by size, whatever nt is;
 //   * the MFMA blur does not read STRIPE_NT;
-//   * resize has no occupancy cap and ignores PassLaunch::nt / wgs.
+//   * resize and orient have no occupancy cap and ignore PassLaunch::nt / wgs.
 inline StreamPolicy stream_policy(const PolicyIn& in) {
   StreamPolicy r;
   const int64_t px = (int64_t)in.rows * in.W;
@@ -311,6 +312,13 @@ inline StreamPolicy stream_policy(const PolicyIn& in) {
     case Family::Resize: {
       // one read of the source frame and one write of the destination, cin channels each
       r.streaming = (px + (int64_t)in.rows2 * in.W2) * in.cin > dev::kNtMinBytes;
+      r.nt_stores = r.streaming;
+      if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
+      break;
+    }
+    case Family::Orient: {
+      // one read of the source window (W x rows) and one write of as many pixels, cin channels each
+      r.streaming = px * 2 * in.cin > dev::kNtMinBytes;
       r.nt_stores = r.streaming;
       if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
       break;

@@ -11,6 +11,7 @@
 
 #include "stripe/chain.h"
 #include "stripe/image.h"
+#include "stripe/orient.h"
 #include "stripe/resize.h"
 
 namespace stripe {
@@ -161,6 +162,52 @@ void launch_resize_kernel(const ResizeLaunch& L, hipStream_t s);  // resize.hip
 // Convenience: builds the two tap tables, uploads them on the stream and launches.
 void resize_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch, int W2,
                    int H2, ResizeMode mode, hipStream_t s);
+
+// Orientation and crop of a whole frame (csrc/hip/orient.hip k_orient; the rule:
+// stripe/orient.h).  Plain 64-bit addressing on arbitrary pitched views: no
+// alignment of base pointers or pitches is assumed, no byte outside the w * C
+// bytes of each source-window row is read and no byte outside the W2 * C bytes
+// of each destination row is written, so a crop is only a view of the source
+// (src + y0 * pitch + x0 * C).
+//
+// `none` and `flipv` copy rows (kOrientCopyRows per workgroup, 16 bytes per
+// lane at the destination's own 16-byte boundaries).  Every other orientation
+// stages a tile of the source in LDS, orient_tile_rows(T) source rows of
+// orient_seg_px(C, T) pixels, and gathers destination dwords from it: the
+// destination tile is seg x rows pixels (w x h) for `fliph` / `rot180` and
+// rows x seg for the transposing four.  For those the LDS image pads behind
+// every group of four rows, so that the four-byte gathers of 32 neighbouring
+// lanes, which are four source rows apart, fall on different banks.
+constexpr int kOrientCopyRows = 4;  // rows per workgroup of the copying instances
+constexpr int orient_tile_rows(bool T) { return T ? 128 : 64; }  // source rows of a tile
+constexpr int orient_seg_px(int C, bool T) {                     // source pixels per tile row
+  return T ? (C == 1 ? 128 : 64) : (C == 1 ? 256 : 128);
+}
+// seg bytes + 3 bytes of address phase
+constexpr int orient_row_dwords(int C, bool T) { return (orient_seg_px(C, T) * C + 3 + 3) / 4; }
+// four rows and the pad
+constexpr int orient_group_dwords(int C, bool T) { return 4 * orient_row_dwords(C, T) + (T ? (C == 1 ? 1 : 2) : 0); }
+constexpr int orient_lds_bytes(int C, bool T) { return orient_tile_rows(T) / 4 * orient_group_dwords(C, T) * 4; }
+struct OrientLaunch {
+  const uint8_t* src = nullptr;  // the source window (already cropped)
+  int64_t src_pitch = 0;
+  int w = 0, h = 0, C = 0;       // the source window, pixels
+  uint8_t* dst = nullptr;        // (T ? h : w) x (T ? w : h) pixels
+  int64_t dst_pitch = 0;
+  Orient op = Orient::None;
+  // optional: the allocations the views lie in (checked against the rows touched)
+  const uint8_t* src_base = nullptr;
+  int64_t src_bytes = 0;
+  const uint8_t* dst_base = nullptr;
+  int64_t dst_bytes = 0;
+};
+void launch_orient(const OrientLaunch& L, hipStream_t s);         // dispatch.cpp: checks, then the kernel
+void launch_orient_kernel(const OrientLaunch& L, hipStream_t s);  // orient.hip
+// Convenience: `crop` is a window of the oriented W x H frame (empty: all of
+// it); maps it to the source window and launches.  dst holds crop.w x crop.h
+// pixels (the whole oriented frame without a crop).
+void orient_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
+                   Orient op, const CropRect& crop, hipStream_t s);
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

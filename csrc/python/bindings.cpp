@@ -21,6 +21,7 @@
 #include "stripe/golden.h"
 #include "stripe/cpu_exec.h"
 #include "stripe/image.h"
+#include "stripe/orient.h"
 #include "stripe/partition.h"
 #include "stripe/rank_net.h"
 
@@ -76,6 +77,15 @@ Histogram hist_from_numpy(const I64Array& a) {
     h.bins[i] = (uint64_t)s[i];
   }
   return h;
+}
+
+// A crop window crosses as None or (x0, y0, w, h).
+CropRect crop_from_py(const py::object& o) {
+  if (o.is_none()) return {};
+  const auto t = o.cast<std::tuple<int, int, int, int>>();
+  CropRect c{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)};
+  STRIPE_CHECK(c.w >= 1 && c.h >= 1, "crop (" << c.x0 << ", " << c.y0 << ", " << c.w << ", " << c.h << "): empty window");
+  return c;
 }
 
 Op stat_op(const std::string& token) {
@@ -310,7 +320,7 @@ PYBIND11_MODULE(_C, m) {
         {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
         {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine},
-        {"resize", policy::Family::Resize}};
+        {"resize", policy::Family::Resize},     {"orient", policy::Family::Orient}};
     const policy::Family* f = nullptr;
     for (const auto& n : names)
       if (family == n.first) f = &n.second;
@@ -339,7 +349,8 @@ PYBIND11_MODULE(_C, m) {
      py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
      py::arg("lut_stage") = false, py::arg("W2") = 0, py::arg("rows2") = 0,
      "the launch decision of a kernel family: sep | sobel_rp | direct | rank | bilateral | conv_small | pointwise | "
-     "pointwise_flat | colormix | blur | combine | resize (W2, rows2: the destination of a resize)");
+     "pointwise_flat | colormix | blur | combine | resize (W2, rows2: the destination of a resize) | orient (W, rows: "
+     "the source window)");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));
 
@@ -442,6 +453,81 @@ PYBIND11_MODULE(_C, m) {
     d["band"] = kResizeBand;
     return d;
   }, "k_resize's tile constants: output bytes per workgroup tile, output rows per band");
+
+  // ---- orientation and crop (stripe/orient.h): a stage in front of the chain, not a chain token ----
+  m.def("orient_names", [] { return orient_names(); }, "the eight orientation names in Exif order (1..8)");
+  m.def("parse_orient", [](const std::string& token) {
+    const Orient o = parse_orient(token);
+    return py::make_tuple(std::string(orient_name(o)), (int)o);
+  }, py::arg("token"), "a name, cw / ccw or exif:N -> (name, bits = T << 2 | FX << 1 | FY)");
+  m.def("orient_compose", [](const std::string& a, const std::string& b) {
+    return std::string(orient_name(orient_compose(parse_orient(a), parse_orient(b))));
+  }, py::arg("a"), py::arg("b"), "the one orientation equal to a, then b");
+  m.def("orient_inverse", [](const std::string& a) { return std::string(orient_name(orient_inverse(parse_orient(a)))); },
+        py::arg("a"));
+  m.def("parse_crop_spec", [](const std::string& spec, int W, int H) {
+    const CropRect c = parse_crop_spec(spec);
+    if (W > 0 || H > 0) check_crop(c, W, H, spec);
+    return py::make_tuple(c.x0, c.y0, c.w, c.h);
+  }, py::arg("spec"), py::arg("W") = 0, py::arg("H") = 0,
+     "'WxH+X+Y' -> (x0, y0, w, h); with W, H (the oriented frame) the window must lie inside it");
+  m.def("orient_source_window", [](const std::string& op, int w, int h, const py::object& crop) {
+    const CropRect c = orient_source_window(parse_orient(op), w, h, crop_from_py(crop));
+    return py::make_tuple(c.x0, c.y0, c.w, c.h);
+  }, py::arg("op"), py::arg("w"), py::arg("h"), py::arg("crop") = py::none(),
+     "the window of the w x h source that the crop of the oriented frame comes from");
+  m.def("golden_orient", [](const U8Array& a, const std::string& op, const py::object& crop) {
+    const Image img = image_from_numpy(a);
+    const Orient o = parse_orient(op);
+    const CropRect c = crop_from_py(crop);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_orient(img, o, c);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("crop") = py::none());
+  m.def("cpu_orient", [](const U8Array& a, const std::string& op, const py::object& crop, int threads) {
+    const Image img = image_from_numpy(a);
+    const Orient o = parse_orient(op);
+    const CropRect c = crop_from_py(crop);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_orient(img, o, c, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("crop") = py::none(), py::arg("threads") = 0);
+  m.def("orient_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int C, uintptr_t dst, int64_t dst_pitch,
+                            const std::string& op, const py::object& crop, uintptr_t stream) {
+    const Orient o = parse_orient(op);
+    const CropRect c = crop_from_py(crop);
+    py::gil_scoped_release nogil;
+    orient_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, C, reinterpret_cast<uint8_t*>(dst),
+                  dst_pitch, o, c, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("C"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("op"), py::arg("crop") = py::none(), py::arg("stream") = 0,
+     "k_orient on pitched device buffers (any alignment), queued on the stream; crop: a window of the oriented frame");
+  m.def("orient_tile", [] {
+    py::dict d;
+    for (int t = 0; t < 2; ++t) {
+      py::dict e;
+      e["rows"] = orient_tile_rows(t);
+      e["seg_gray"] = orient_seg_px(1, t);
+      e["seg_rgb"] = orient_seg_px(3, t);
+      e["lds_gray"] = orient_lds_bytes(1, t);
+      e["lds_rgb"] = orient_lds_bytes(3, t);
+      d[t ? "transposing" : "fx"] = e;
+    }
+    d["copy_rows"] = kOrientCopyRows;
+    d["cpu_tile"] = kCpuOrientTile;
+    return d;
+  }, "k_orient's tile constants, for the FX and the transposing instances: source rows of a tile, source pixels "
+     "per tile row (gray / RGB), LDS bytes; rows per workgroup of the copying instances; cpu_orient's tile side");
+  m.def("jpeg_orientation", [](py::bytes b) {
+    const std::string s(b);
+    return jpeg_orientation(reinterpret_cast<const uint8_t*>(s.data()), s.size());
+  }, py::arg("data"), "Exif Orientation (1..8) of a JPEG stream; 1 when it carries no well-formed one");
 
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },

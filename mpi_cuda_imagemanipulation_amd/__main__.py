@@ -6,6 +6,7 @@ gray -> contrast -> emboss, gather, write) is `run --preset ref-gpu`.
   python -m mpi_cuda_imagemanipulation_amd run --input in.jpg --output out.png \\
       --chain gray:ref,contrast:3.5,emboss3 --ranks 4 --backend local
   python -m mpi_cuda_imagemanipulation_amd run --input in.jpg --output out.png --resize 1920x1080 --chain sharpen
+  python -m mpi_cuda_imagemanipulation_amd run --input phone.jpg --output out.png --orient auto --crop 800x600+40+0
   python -m mpi_cuda_imagemanipulation_amd convert in.jpg out.ppm
   python -m mpi_cuda_imagemanipulation_amd filters
 
@@ -54,6 +55,12 @@ def main(argv=None) -> int:
     r.add_argument("--resize", default=None, metavar="WxH[:mode]",
                    help="resize the loaded frame before the chain (mode: auto | nearest | bilinear | area); "
                         "on the GPU for GPU backends, on the host executor for host / gloo")
+    r.add_argument("--orient", default=None, metavar="OP|auto",
+                   help="orient the loaded frame before --resize and the chain: none | fliph | rot180 | flipv | "
+                        "transpose | rot90 (cw) | transverse | rot270 (ccw) | exif:N | auto (the Exif Orientation "
+                        "of a JPEG input, none for any other format); without it the stored pixels are used")
+    r.add_argument("--crop", default=None, metavar="WxH+X+Y",
+                   help="a window of the oriented frame, cut in the same pass")
     r.add_argument("--verbose", "-v", action="store_true", help="rank-prefixed progress log on stderr")
     c = sub.add_parser("convert", help="convert between image formats")
     c.add_argument("src")
@@ -86,6 +93,7 @@ def main(argv=None) -> int:
         import torch
 
         backend = "local" if torch.cuda.is_available() else "host"
+    img, oriented = _orient_input(a, img, backend != "host")
     img, resized_from = _resize_input(a, img, backend != "host")
     t0 = time.perf_counter()
     log = utils.get_logger("cli", 0)
@@ -95,8 +103,35 @@ def main(argv=None) -> int:
     utils.write_image(a.output, out)
     print(json.dumps({"cmd": "run", "input": a.input, "output": a.output, "shape": list(img.shape),
                       "chain": pipe.spec.chain, "ranks": a.ranks, "backend": backend, "wall_ms": round(ms, 3),
-                      **({"resized_from": resized_from} if resized_from else {})}))
+                      **oriented, **({"resized_from": resized_from} if resized_from else {})}))
     return 0
+
+
+def _orient_input(a, img, on_gpu):
+    """--orient OP|auto and --crop WxH+X+Y on the loaded frame, one pass: (frame, JSON members)."""
+    if not a.orient and not a.crop:
+        return img, {}
+    import numpy as np
+
+    from . import ops
+    from ._native import C
+
+    token = a.orient or "none"
+    if token == "auto":
+        token = f"exif:{ops.exif_orientation(a.input)}"
+    name = C.parse_orient(token)[0]
+    H, W = img.shape[:2]
+    crop = None
+    if a.crop:
+        ow, oh = (H, W) if C.parse_orient(name)[1] & 4 else (W, H)
+        crop = C.parse_crop_spec(a.crop, ow, oh)
+    if on_gpu:
+        import torch
+
+        out = ops.orient(torch.from_numpy(np.ascontiguousarray(img)).cuda(), name, crop).cpu().numpy()
+    else:
+        out = ops.orient(np.ascontiguousarray(img), name, crop)
+    return out, {"oriented": name, "cropped_from": [int(W), int(H)]}
 
 
 def _resize_input(a, img, on_gpu):
@@ -131,7 +166,9 @@ def _run_per_process(a, pipe) -> int:
     log = utils.get_logger("cli", ctx.rank)
     img = utils.read_image(a.input) if ctx.rank == 0 else None
     resized_from = None
-    if ctx.rank == 0:  # rank 0 resizes before it broadcasts the geometry
+    oriented = {}
+    if ctx.rank == 0:  # rank 0 orients, crops and resizes before it broadcasts the geometry
+        img, oriented = _orient_input(a, img, a.backend in ("rccl", "gloo-gpu"))
         img, resized_from = _resize_input(a, img, a.backend in ("rccl", "gloo-gpu"))
     meta = [None if img is None else tuple(img.shape)]
     if ctx.world > 1:
@@ -161,7 +198,7 @@ def _run_per_process(a, pipe) -> int:
         print(json.dumps({"cmd": "run", "input": a.input, "output": a.output, "shape": list(shape),
                           "chain": pipe.spec.chain, "ranks": ctx.world, "backend": a.backend,
                           "stripe_rows": dp.stripe[1], "dist_ms": round(ms, 3),
-                          **({"resized_from": resized_from} if resized_from else {})}))
+                          **oriented, **({"resized_from": resized_from} if resized_from else {})}))
     if ctx.world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -486,6 +486,118 @@ def resize_reference(x, size=None, scale=None, mode: str = "auto"):
     return out[:, :, None] if keep else out
 
 
+# ---- orientation and crop: a stage in front of the chain, not a chain token ---------
+ORIENTATIONS = tuple(C.orient_names())
+
+
+def _crop_tuple(crop):
+    if crop is None:
+        return None
+    try:
+        x0, y0, w, h = (int(v) for v in crop)
+    except (TypeError, ValueError):
+        raise ValueError(f"crop must be (x0, y0, w, h), got {crop!r}") from None
+    return x0, y0, w, h
+
+
+def _oriented_shape(H, W, name, crop):
+    oh, ow = (W, H) if C.parse_orient(name)[1] & 4 else (H, W)
+    if crop is None:
+        return oh, ow
+    x0, y0, w, h = crop
+    if not (w >= 1 and h >= 1 and x0 >= 0 and y0 >= 0 and x0 + w <= ow and y0 + h <= oh):
+        raise ValueError(f"crop {w}x{h}+{x0}+{y0} is empty or leaves the oriented frame of {ow}x{oh}")
+    return h, w
+
+
+def orient(x, op: str = "none", crop=None):
+    """One of the eight orientations of the rectangle, then an optional crop, in one pass.
+
+    op: "none", "fliph", "rot180", "flipv", "transpose", "rot90" (clockwise, alias "cw"),
+    "transverse", "rot270" (alias "ccw") or "exif:N" (the operation that shows an image stored with
+    Exif Orientation N upright).  crop=(x0, y0, w, h) is a window of the oriented frame.  CUDA uint8
+    tensors run on the k_orient HIP kernel on torch's current stream (rows of a strided view are
+    read in place), numpy arrays / CPU tensors on the threaded host executor, bit-identical to
+    `orient_reference`.  A BxHxWxC batch runs frame by frame."""
+    name = C.parse_orient(op)[0]
+    crop = _crop_tuple(crop)
+    if x.ndim == 4:
+        if x.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
+        outs = [orient(x[b], name, crop) for b in range(x.shape[0])]
+        if outs:
+            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
+        shape = (0,) + _oriented_shape(x.shape[1], x.shape[2], name, crop) + (x.shape[3],)
+        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
+    W, H, Cc = _shape(x)
+    H2, W2 = _oriented_shape(H, W, name, crop)
+    if _is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        # the kernel takes pitched views: only the pixels of a row must be packed
+        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
+        xc = x if packed else x.contiguous()
+        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            C.orient_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, name, crop,
+                            stream.cuda_stream)
+        # keep the input alive until the stream has consumed it
+        xc.record_stream(stream)
+        return out
+    was_tensor = _is_tensor(x)
+    arr = x.numpy() if was_tensor else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.cpu_orient(np.ascontiguousarray(arr[:, :, 0] if keep else arr), name, crop)
+    if keep:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if was_tensor else out
+
+
+def orient_reference(x, op: str = "none", crop=None):
+    """Golden CPU result of `orient`: the rule as a plain per-pixel loop."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _shape(arr)
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.golden_orient(np.ascontiguousarray(arr[:, :, 0] if keep else arr), C.parse_orient(op)[0], _crop_tuple(crop))
+    return out[:, :, None] if keep else out
+
+
+def flip(x, axis):
+    """Flip along axis 0 (rows: `flipv`), axis 1 (columns: `fliph`) or both, (0, 1) (`rot180`)."""
+    axes = (axis,) if np.isscalar(axis) else tuple(axis)
+    if not axes or any(a not in (0, 1) for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"axis must be 0, 1 or (0, 1), got {axis!r}")
+    return orient(x, {(0,): "flipv", (1,): "fliph"}.get(axes, "rot180"))
+
+
+def rot90(x, k: int = 1):
+    """k counter-clockwise quarter turns, like np.rot90 / torch.rot90 on the first two axes (any integer k)."""
+    return orient(x, ("none", "rot270", "rot180", "rot90")[int(k) % 4])
+
+
+def transpose_image(x):
+    """Rows become columns (`transpose`)."""
+    return orient(x, "transpose")
+
+
+def crop(x, x0, y0, w, h):
+    """The window of w x h pixels whose top-left pixel is (x0, y0)."""
+    return orient(x, "none", (x0, y0, w, h))
+
+
+def exif_orientation(path_or_bytes) -> int:
+    """Exif Orientation (1..8) of a JPEG file or byte string; 1 when it carries none (or is no JPEG)."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    return C.jpeg_orientation(data)
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -500,4 +612,5 @@ __all__ = [
     "unsharp_mask", "morph_gradient", "top_hat", "black_hat", "adaptive_threshold",
     "combine", "absdiff", "add", "subtract", "blend", "minimum", "maximum",
     "resize", "resize_reference", "RESIZE_MODES",
+    "orient", "orient_reference", "flip", "rot90", "transpose_image", "crop", "exif_orientation", "ORIENTATIONS",
 ]

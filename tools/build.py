@@ -49,6 +49,7 @@ CORE_SOURCES = [
     "core/golden.cpp",
     "core/cpu_exec.cpp",
     "core/resize.cpp",
+    "core/orient.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -63,6 +64,7 @@ CORE_SOURCES = [
     "hip/histogram.hip",
     "hip/combine.hip",
     "hip/resize.hip",
+    "hip/orient.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
