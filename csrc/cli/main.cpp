@@ -20,6 +20,7 @@
 //   stripe cmp   a.ppm b.ppm [--tol 0]
 //   stripe gen   --synthetic WxHxC --seed S --output x.ppm
 //   stripe convert --input a.jpg --output b.ppm [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]
+//                  [--rotate DEG[:same|fit] | --warp "a;b;c;d;e;f[:WxH]"] [--warp-mode M] [--warp-border B]
 //                  [--resize WxH[:mode]]
 //   stripe info  [--chain ...] [--channels C] [--format json]
 #include <hip/hip_runtime.h>
@@ -354,6 +355,74 @@ std::string orient_input(const Args& a, Input* in, const std::string& path, bool
          std::to_string(H0) + "]";
 }
 
+// --rotate DEG[:same|fit] or --warp "a;b;c;d;e;f[:WxH]" (the forward matrix),
+// with --warp-mode bilinear|nearest and --warp-border constant[:V]|replicate:
+// the frame is warped after --orient / --crop and before --resize and the
+// chain: on the GPU (k_warp) for device backends, on cpu_warp for the host
+// backend.  `token` gets the canonical form of the request.
+bool warp_requested(const Args& a) {
+  STRIPE_CHECK(!(a.has("rotate") && a.has("warp")), "--rotate and --warp are mutually exclusive");
+  STRIPE_CHECK(a.has("rotate") || a.has("warp") || (!a.has("warp-mode") && !a.has("warp-border")),
+               "--warp-mode and --warp-border need --rotate or --warp");
+  return a.has("rotate") || a.has("warp");
+}
+
+WarpMap warp_map_of(const Args& a, int W, int H, std::string* token) {
+  const WarpMode mode = parse_warp_mode(a.get("warp-mode", "bilinear"));
+  WarpBorder border;
+  uint8_t fill;
+  parse_warp_border(a.get("warp-border", "constant"), &border, &fill);
+  if (a.has("rotate")) {
+    const RotateSpec r = parse_rotate_spec(a.get("rotate"));
+    const Rotation rot = rotate_matrix(r.deg, r.fit, W, H);
+    if (token) *token = rotate_token(r);
+    return warp_quantise(rot.minv, true, W, H, rot.W2, rot.H2, mode, border, fill, a.get("rotate"));
+  }
+  const WarpSpec s = parse_warp_spec(a.get("warp"));
+  const int W2 = s.W2 > 0 ? s.W2 : W, H2 = s.H2 > 0 ? s.H2 : H;
+  if (token) *token = warp_token(s, W2, H2);
+  return warp_quantise(s.M, false, W, H, W2, H2, mode, border, fill, a.get("warp"));
+}
+
+Image warp_image(const Image& in, const WarpMap& m, bool on_device, int device) {
+  if (!on_device) return cpu_warp(in, m, cpu_threads());
+  HIP_CHECK(hipSetDevice(device));
+  Image out(m.W2, m.H2, in.C, NoInit{});
+  uint8_t *ds = nullptr, *dd = nullptr;
+  try {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
+    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
+    warp_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), m, nullptr);
+    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipFree(ds);
+    (void)hipFree(dd);
+    throw;
+  }
+  HIP_CHECK(hipFree(ds));
+  HIP_CHECK(hipFree(dd));
+  return out;
+}
+
+// Applies --rotate / --warp to the loaded input (a JPEG's coefficients are
+// decoded to pixels first); returns the JSON members that record the stage, or "".
+std::string warp_input(const Args& a, Input* in, bool on_device, int device) {
+  if (!warp_requested(a)) return "";
+  const int W0 = in->W, H0 = in->H;
+  std::string token;
+  const WarpMap m = warp_map_of(a, W0, H0, &token);
+  if (in->coefs) {
+    in->img = jpeg_pixels(std::move(in->jpeg));
+    in->jpeg = JpegCoefs{};
+    in->coefs = false;
+  }
+  in->img = warp_image(in->img, m, on_device, device);
+  in->W = in->img.W;
+  in->H = in->img.H;
+  return ",\"warped_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "],\"warp\":\"" + token + "\"";
+}
+
 // One rank of a multi-process job: `stripe run --backend rccl --world N --rank r
 // --rendezvous FILE [--device d]` (like the reference's `mpiexec -n N`, one
 // process per rank; only rank 0 reads the input and writes the output).
@@ -370,6 +439,7 @@ int cmd_run_rank(const Args& a) {
     STRIPE_CHECK(a.has("input") && a.has("output"), "rank 0 needs --input and --output");
     in = read_input(a.get("input"), true);
     resized = orient_input(a, &in, a.get("input"), true, device);  // before the geometry is broadcast
+    resized += warp_input(a, &in, true, device);
     resized += resize_input(a, &in, true, device);
     cfg = config_from(a, in.W, in.H, in.C);
   } else {
@@ -411,6 +481,7 @@ int cmd_run(const Args& a) {
   Input in = read_input(a.get("input"), !host_run);
   const std::vector<int> rdevs = parse_int_list(a.get("devices"));
   const std::string resized = orient_input(a, &in, a.get("input"), !host_run, rdevs.empty() ? 0 : rdevs[0]) +
+                              warp_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]) +
                               resize_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]);
   const double read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
   EngineConfig cfg = config_from(a, in.W, in.H, in.C);
@@ -431,6 +502,8 @@ int cmd_run(const Args& a) {
       const Orient hop = orient_of(a, a.get("held"));
       held = orient_image(held, hop, crop_of(a, hop, held.W, held.H), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     }
+    if (warp_requested(a))  // the held image gets the same warp
+      held = warp_image(held, warp_map_of(a, held.W, held.H, nullptr), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     if (a.has("resize"))  // the held image is resized the same way
       held = resize_image(held, parse_resize_spec(a.get("resize")), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
@@ -516,6 +589,7 @@ int cmd_convert(const Args& a) {
   const bool host_run = a.get("backend", device_count() > 0 ? "local" : "host") == "host";
   const std::vector<int> devs = parse_int_list(a.get("devices"));
   const std::string resized = orient_input(a, &in, a.get("input"), !host_run, devs.empty() ? 0 : devs[0]) +
+                              warp_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]) +
                               resize_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]);
   const Image& img = in.img;
   write_image(a.get("output"), img, a.geti("quality", 95));
@@ -845,6 +919,10 @@ void usage() {
                "        [--orient none|fliph|rot180|flipv|transpose|rot90|transverse|rot270|exif:N|auto] [--crop WxH+X+Y]\n"
                "            (the frame, and --held's, oriented and cropped before --resize and the chain; auto: the\n"
                "             Exif Orientation of a JPEG input; --crop is a window of the oriented frame)\n"
+               "        [--rotate DEG[:same|fit] | --warp \"a;b;c;d;e;f[:WxH]\"] [--warp-mode bilinear|nearest]\n"
+               "        [--warp-border constant[:V]|replicate]\n"
+               "            (the frame, and --held's, rotated counter-clockwise about its centre or warped by the forward\n"
+               "             2x3 matrix, after --orient / --crop and before --resize; fit: the frame grows to hold the turn)\n"
                "        [--resize WxH[:auto|nearest|bilinear|area]]  (the frame, and --held's, resized before the chain)\n"
                "        one process per rank: --backend rccl --world N --rank r --rendezvous FILE [--device d]\n"
                "  bench --synthetic WxHxC [--seed S] [--chain C] [--ranks 1,2,4,8] [--iters N] [--warmup N]\n"
@@ -855,6 +933,7 @@ void usage() {
                "  cmp   a.ppm b.ppm [--tol T]\n"
                "  gen   --synthetic WxHxC [--seed S] --output out.ppm|out.jpg\n"
                "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]\n"
+               "        [--rotate DEG[:same|fit] | --warp \"a;b;c;d;e;f[:WxH]\"] [--warp-mode M] [--warp-border B]\n"
                "        [--resize WxH[:mode]] [--backend host]\n"
                "  info  [--chain C] [--channels C] [--format json]\n");
 }

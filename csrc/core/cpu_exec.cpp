@@ -14,6 +14,7 @@
 #include "stripe/orient.h"
 #include "stripe/rank_net.h"
 #include "stripe/resize.h"
+#include "stripe/warp.h"
 
 namespace stripe {
 
@@ -712,6 +713,115 @@ Image cpu_orient(const Image& in, Orient op, const CropRect& crop, int threads) 
   Image out(orient_t(op) ? s.h : s.w, orient_t(op) ? s.w : s.h, in.C, NoInit{});
   cpu_orient(in.row(s.y0) + (size_t)s.x0 * in.C, in.row_bytes(), s.w, s.h, in.C, out.data.data(), out.row_bytes(), op,
              threads);
+  return out;
+}
+
+// ---- affine warp (stripe/warp.h) ----
+namespace {
+inline int64_t floor_div64(int64_t n, int64_t d) {  // d > 0
+  const int64_t q = n / d;
+  return n % d < 0 ? q - 1 : q;
+}
+inline int64_t ceil_div64(int64_t n, int64_t d) { return -floor_div64(-n, d); }
+
+// the integers x of [*x0, *x1) with lo <= a * x + c < hi, intersected with what [*x0, *x1) held
+void linear_span(int64_t a, int64_t c, int64_t lo, int64_t hi, int* x0, int* x1) {
+  int64_t b0 = *x0, b1 = *x1;
+  if (a == 0) {
+    if (c < lo || c >= hi) b1 = b0;
+  } else if (a > 0) {
+    b0 = std::max(b0, ceil_div64(lo - c, a));
+    b1 = std::min(b1, ceil_div64(hi - c, a));
+  } else {
+    b0 = std::max(b0, floor_div64(c - hi, -a) + 1);
+    b1 = std::min(b1, floor_div64(c - lo, -a) + 1);
+  }
+  b0 = std::min<int64_t>(b0, *x1);  // (an empty span stays inside the old one)
+  *x0 = (int)b0;
+  *x1 = (int)std::max(b0, b1);
+}
+
+// output pixels [xa, xb) of row y; INSIDE: every tap lies inside the frame
+template <int C, bool BIL, bool INSIDE>
+void warp_span(const uint8_t* src, int64_t sp, int W, int H, uint8_t* drow, const WarpMap& m, int y, int xa, int xb) {
+  const bool rep = m.border == WarpBorder::Replicate;
+  const uint32_t fill = m.fill;
+  auto tap = [&](int iy, int ix, int ch) -> uint32_t {
+    if constexpr (!INSIDE) {
+      if (rep) {
+        iy = std::min(std::max(iy, 0), H - 1);
+        ix = std::min(std::max(ix, 0), W - 1);
+      } else if (ix < 0 || iy < 0 || ix >= W || iy >= H) {
+        return fill;
+      }
+    }
+    return src[(int64_t)iy * sp + (int64_t)ix * C + ch];
+  };
+  int64_t sx = warp_sx(m, xa, y), sy = warp_sy(m, xa, y);
+  uint8_t* o = drow + (size_t)xa * C;
+  for (int x = xa; x < xb; ++x, sx += m.A[0][0], sy += m.A[1][0], o += C) {
+    if constexpr (BIL) {
+      const int64_t X = (sx + (1 << 15)) >> 16, Y = (sy + (1 << 15)) >> 16;
+      const int ix = (int)(X >> 8), iy = (int)(Y >> 8);
+      const uint32_t fx = (uint32_t)(X & 255), fy = (uint32_t)(Y & 255);
+      for (int ch = 0; ch < C; ++ch)
+        o[ch] = (uint8_t)warp_bilinear(tap(iy, ix, ch), tap(iy, ix + 1, ch), tap(iy + 1, ix, ch),
+                                       tap(iy + 1, ix + 1, ch), fx, fy);
+    } else {
+      const int ix = (int)((sx + (1 << 23)) >> 24), iy = (int)((sy + (1 << 23)) >> 24);
+      for (int ch = 0; ch < C; ++ch) o[ch] = (uint8_t)tap(iy, ix, ch);
+    }
+  }
+}
+
+template <int C, bool BIL>
+void warp_rows(const uint8_t* src, int64_t sp, int W, int H, uint8_t* dst, int64_t dp, const WarpMap& m, int ya, int yb) {
+  // every tap inside the frame: lo <= sx < hix and lo <= sy < hiy (bilinear: ix >= 0 and ix + 1 <= W - 1)
+  const int64_t lo = BIL ? -(int64_t(1) << 15) : -(int64_t(1) << 23);
+  const int64_t hix = ((int64_t)(BIL ? W - 1 : W) << 24) + lo, hiy = ((int64_t)(BIL ? H - 1 : H) << 24) + lo;
+  for (int y = ya; y < yb; ++y) {
+    int x0 = 0, x1 = m.W2;
+    linear_span(m.A[0][0], (int64_t)m.A[0][1] * y + m.B[0], lo, hix, &x0, &x1);
+    linear_span(m.A[1][0], (int64_t)m.A[1][1] * y + m.B[1], lo, hiy, &x0, &x1);
+    uint8_t* drow = dst + (int64_t)y * dp;
+    if (x1 <= x0) {
+      warp_span<C, BIL, false>(src, sp, W, H, drow, m, y, 0, m.W2);
+      continue;
+    }
+    warp_span<C, BIL, false>(src, sp, W, H, drow, m, y, 0, x0);
+    warp_span<C, BIL, true>(src, sp, W, H, drow, m, y, x0, x1);
+    warp_span<C, BIL, false>(src, sp, W, H, drow, m, y, x1, m.W2);
+  }
+}
+}  // namespace
+
+void cpu_warp(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
+              const WarpMap& m, int threads) {
+  STRIPE_CHECK(C == 1 || C == 3, "warp: image must have 1 or 3 channels, got C = " << C);
+  STRIPE_CHECK(src && dst, "warp: empty image");
+  STRIPE_CHECK(W >= 1 && H >= 1 && W <= kWarpMaxSize && H <= kWarpMaxSize,
+               "warp: source size " << W << "x" << H << " outside 1.." << kWarpMaxSize);
+  STRIPE_CHECK(m.W2 >= 1 && m.H2 >= 1 && m.W2 <= kWarpMaxSize && m.H2 <= kWarpMaxSize,
+               "warp: destination size " << m.W2 << "x" << m.H2 << " outside 1.." << kWarpMaxSize);
+  STRIPE_CHECK(src_pitch >= (int64_t)W * C && dst_pitch >= (int64_t)m.W2 * C, "warp: pitch smaller than a row");
+  const bool bil = m.mode == WarpMode::Bilinear;
+  parallel_rows(0, m.H2, (bil ? 5 : 2) * (int64_t)m.W2 * C, std::max(1, threads), [&](int ya, int yb) {
+    if (C == 1) {
+      if (bil) warp_rows<1, true>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+      else warp_rows<1, false>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+    } else {
+      if (bil) warp_rows<3, true>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+      else warp_rows<3, false>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+    }
+  });
+}
+
+Image cpu_warp(const Image& in, const WarpMap& m, int threads) {
+  STRIPE_CHECK(in.C == 1 || in.C == 3, "warp: image must have 1 or 3 channels, got C = " << in.C);
+  STRIPE_CHECK(m.W2 >= 1 && m.H2 >= 1 && m.W2 <= kWarpMaxSize && m.H2 <= kWarpMaxSize,
+               "warp: destination size " << m.W2 << "x" << m.H2 << " outside 1.." << kWarpMaxSize);
+  Image out(m.W2, m.H2, in.C, NoInit{});
+  cpu_warp(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), m, threads);
   return out;
 }
 

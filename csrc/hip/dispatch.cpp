@@ -158,6 +158,41 @@ void launch_orient(const OrientLaunch& L, hipStream_t s) {
   launch_orient_kernel(L, s);
 }
 
+void launch_warp(const WarpLaunch& L, hipStream_t s) {
+  // host-side shape checks before the kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad warp launch: null src or dst");
+  STRIPE_CHECK(L.C == 1 || L.C == 3, "warp needs 1 or 3 channels, got C = " << L.C);
+  STRIPE_CHECK(L.W >= 1 && L.W <= kWarpMaxSize && L.H >= 1 && L.H <= kWarpMaxSize,
+               "warp: source size " << L.W << "x" << L.H << " outside 1.." << kWarpMaxSize);
+  const WarpMap& m = L.map;
+  STRIPE_CHECK(m.W2 >= 1 && m.W2 <= kWarpMaxSize && m.H2 >= 1 && m.H2 <= kWarpMaxSize,
+               "warp: destination size " << m.W2 << "x" << m.H2 << " outside 1.." << kWarpMaxSize);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "warp: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)m.W2 * L.C, "warp: dst_pitch " << L.dst_pitch << " < row bytes " << m.W2 * L.C);
+  // the quantiser's ranges: every term of the map stays below 2^48
+  for (int i = 0; i < 2; ++i) {
+    STRIPE_CHECK(m.A[i][0] > -(int64_t(64) << kWarpQ) && m.A[i][0] < (int64_t(64) << kWarpQ) &&
+                     m.A[i][1] > -(int64_t(64) << kWarpQ) && m.A[i][1] < (int64_t(64) << kWarpQ),
+                 "warp: map coefficient outside (-64, 64)");
+    STRIPE_CHECK(m.B[i] > -(int64_t(1) << (20 + kWarpQ)) && m.B[i] < (int64_t(1) << (20 + kWarpQ)),
+                 "warp: map offset outside (-2^20, 2^20)");
+  }
+  STRIPE_CHECK((int)m.mode >= 0 && (int)m.mode < 2 && (int)m.border >= 0 && (int)m.border < 2,
+               "warp: bad mode or border");
+  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
+  // Where the caller names the allocations, the rows touched lie inside them.
+  if (L.src_base)
+    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
+                                            L.src_bytes,
+                 "warp: source rows outside their buffer");
+  if (L.dst_base)
+    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(m.H2 - 1) * L.dst_pitch +
+                                                (int64_t)m.W2 * L.C <= L.dst_bytes,
+                 "warp: destination rows outside their buffer");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_warp_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

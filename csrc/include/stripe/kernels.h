@@ -13,6 +13,7 @@
 #include "stripe/image.h"
 #include "stripe/orient.h"
 #include "stripe/resize.h"
+#include "stripe/warp.h"
 
 namespace stripe {
 
@@ -208,6 +209,58 @@ void launch_orient_kernel(const OrientLaunch& L, hipStream_t s);  // orient.hip
 // pixels (the whole oriented frame without a crop).
 void orient_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
                    Orient op, const CropRect& crop, hipStream_t s);
+
+// Affine warp of a whole frame (csrc/hip/warp.hip k_warp; the rule:
+// stripe/warp.h).  Addressing as k_orient: 64-bit on arbitrary pitched views,
+// no alignment assumed, no byte outside the W * C bytes of a source row read,
+// no byte outside the W2 * C bytes of a destination row written.
+//
+// A workgroup owns a destination tile of kWarpTile x kWarpTile pixels; a lane
+// computes four neighbouring pixels of a row and stores them as dwords.  Two
+// instances per (C, mode, border, nt):
+//   * staged: the exact integer map at the tile's four corners bounds the
+//     source box (the map is affine), which is clipped to the frame and staged
+//     in LDS, kWarpBox rows of kWarpBox pixels at most (16-byte loads from each
+//     row's own first byte, single bytes at its end); the taps are gathered
+//     from LDS.  kWarpBox covers every rotation at scale <= 1: a row of A with
+//     |A[i][0]| + |A[i][1]| <= sqrt(2) * 2^24 spans floor(63 * sqrt(2)) = 89
+//     pixels over a tile, + 1 for the rounding of the two ends, + 1 for the
+//     tap, + 1 for the count.
+//   * direct: per-tap global byte loads with the same arithmetic, for every
+//     other map (strong minification), so that no valid map is refused.
+// warp_plan is the choice, from A and the tile constants alone.
+constexpr int kWarpTile = 64;  // destination pixels per tile side
+constexpr int kWarpBox = 92;   // source pixels per side of the staged box, at most
+// bytes of a staged row in LDS: the box's bytes in whole dwords, an odd number of
+// them (23 gray, 69 RGB), so that a gather that walks down the rows (a quarter
+// turn) spreads over the banks
+constexpr int warp_row_bytes(int C) { return (((kWarpBox * C + 3) / 4) | 1) * 4; }
+constexpr int warp_lds_bytes(int C) { return kWarpBox * warp_row_bytes(C); }
+// pixels a row of A spans over a tile, taps and rounding included
+inline int64_t warp_box_span(int32_t a0, int32_t a1) {
+  const int64_t s = (int64_t)(kWarpTile - 1) * ((a0 < 0 ? -(int64_t)a0 : a0) + (a1 < 0 ? -(int64_t)a1 : a1));
+  return (s >> kWarpQ) + 3;
+}
+inline bool warp_plan_staged(const WarpMap& m) {
+  return warp_box_span(m.A[0][0], m.A[0][1]) <= kWarpBox && warp_box_span(m.A[1][0], m.A[1][1]) <= kWarpBox;
+}
+struct WarpLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int W = 0, H = 0, C = 0;  // the source, pixels
+  uint8_t* dst = nullptr;   // map.W2 x map.H2 pixels
+  int64_t dst_pitch = 0;
+  WarpMap map;
+  // optional: the allocations the views lie in (checked against the rows touched)
+  const uint8_t* src_base = nullptr;
+  int64_t src_bytes = 0;
+  const uint8_t* dst_base = nullptr;
+  int64_t dst_bytes = 0;
+};
+void launch_warp(const WarpLaunch& L, hipStream_t s);         // dispatch.cpp: checks, then the kernel
+void launch_warp_kernel(const WarpLaunch& L, hipStream_t s);  // warp.hip
+void warp_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
+                 const WarpMap& map, hipStream_t s);
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

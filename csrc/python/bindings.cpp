@@ -320,7 +320,8 @@ PYBIND11_MODULE(_C, m) {
         {"conv_small", policy::Family::ConvSmall}, {"pointwise", policy::Family::PointwiseChan},
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
         {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine},
-        {"resize", policy::Family::Resize},     {"orient", policy::Family::Orient}};
+        {"resize", policy::Family::Resize},     {"orient", policy::Family::Orient},
+        {"warp", policy::Family::Warp}};
     const policy::Family* f = nullptr;
     for (const auto& n : names)
       if (family == n.first) f = &n.second;
@@ -350,7 +351,7 @@ PYBIND11_MODULE(_C, m) {
      py::arg("lut_stage") = false, py::arg("W2") = 0, py::arg("rows2") = 0,
      "the launch decision of a kernel family: sep | sobel_rp | direct | rank | bilateral | conv_small | pointwise | "
      "pointwise_flat | colormix | blur | combine | resize (W2, rows2: the destination of a resize) | orient (W, rows: "
-     "the source window)");
+     "the source window) | warp (W, rows: the source; W2, rows2: the destination)");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));
 
@@ -528,6 +529,117 @@ PYBIND11_MODULE(_C, m) {
     const std::string s(b);
     return jpeg_orientation(reinterpret_cast<const uint8_t*>(s.data()), s.size());
   }, py::arg("data"), "Exif Orientation (1..8) of a JPEG stream; 1 when it carries no well-formed one");
+
+  // ---- affine warp (stripe/warp.h): a stage in front of the chain, not a chain token ----
+  // A quantised map travels as its six integers (A00, A01, B0, A10, A11, B1) and the destination size.
+  static const auto warp_map_from_py = [](const std::vector<int64_t>& q, int W2, int H2, const std::string& mode,
+                                          const std::string& border, int fill) {
+    STRIPE_CHECK(q.size() == 6, "warp: a quantised map is six integers (A00, A01, B0, A10, A11, B1), got " << q.size());
+    STRIPE_CHECK(fill >= 0 && fill <= 255, "warp: the fill value must be in 0..255, got " << fill);
+    WarpMap m;
+    const int64_t lim = int64_t(64) << kWarpQ;
+    for (int i = 0; i < 2; ++i) {
+      STRIPE_CHECK(q[3 * i] > -lim && q[3 * i] < lim && q[3 * i + 1] > -lim && q[3 * i + 1] < lim,
+                   "warp: map coefficient outside (-64, 64)");
+      STRIPE_CHECK(q[3 * i + 2] > -(int64_t(1) << (20 + kWarpQ)) && q[3 * i + 2] < (int64_t(1) << (20 + kWarpQ)),
+                   "warp: map offset outside (-2^20, 2^20)");
+      m.A[i][0] = (int32_t)q[3 * i], m.A[i][1] = (int32_t)q[3 * i + 1], m.B[i] = q[3 * i + 2];
+    }
+    m.W2 = W2, m.H2 = H2;
+    m.mode = parse_warp_mode(mode);
+    if (border == "constant") m.border = WarpBorder::Constant, m.fill = (uint8_t)fill;
+    else if (border == "replicate") m.border = WarpBorder::Replicate;
+    else fail("warp: unknown border '" + border + "' (constant | replicate)");
+    return m;
+  };
+  m.def("warp_quantise", [](const std::vector<double>& M, bool inverse, int W, int H, int W2, int H2,
+                            const std::string& token) {
+    STRIPE_CHECK(M.size() == 6, "warp: a matrix is six numbers a, b, c, d, e, f (row-major 2 x 3), got " << M.size());
+    const WarpMap q = warp_quantise(M.data(), inverse, W, H, W2 > 0 ? W2 : W, H2 > 0 ? H2 : H, WarpMode::Bilinear,
+                                    WarpBorder::Constant, 0, token);
+    return py::make_tuple((int64_t)q.A[0][0], (int64_t)q.A[0][1], q.B[0], (int64_t)q.A[1][0], (int64_t)q.A[1][1], q.B[1],
+                          q.W2, q.H2);
+  }, py::arg("M"), py::arg("inverse") = false, py::arg("W") = 1, py::arg("H") = 1, py::arg("W2") = 0,
+     py::arg("H2") = 0, py::arg("token") = "matrix",
+     "(A00, A01, B0, A10, A11, B1, W2, H2): the Q24 inverse map of the forward (or, inverse=True, the inverse) "
+     "matrix; W2, H2 = 0: the source's size");
+  m.def("rotate_matrix", [](double deg, bool fit, int W, int H) {
+    const Rotation r = rotate_matrix(deg, fit, W, H);
+    return py::make_tuple(std::vector<double>(r.minv, r.minv + 6), r.W2, r.H2);
+  }, py::arg("deg"), py::arg("fit"), py::arg("W"), py::arg("H"),
+     "(inverse matrix, W2, H2) of a counter-clockwise rotation about the source centre");
+  m.def("parse_warp_spec", [](const std::string& spec) {
+    const WarpSpec s = parse_warp_spec(spec);
+    return py::make_tuple(std::vector<double>(s.M, s.M + 6), s.W2, s.H2);
+  }, py::arg("spec"), "'a;b;c;d;e;f[:WxH]' -> (forward matrix, W2, H2); 0, 0 without a size");
+  m.def("parse_rotate_spec", [](const std::string& spec) {
+    const RotateSpec r = parse_rotate_spec(spec);
+    return py::make_tuple(r.deg, r.fit, rotate_token(r));
+  }, py::arg("spec"), "'DEG[:same|fit]' -> (deg, fit, canonical token)");
+  m.def("warp_token", [](const std::vector<double>& M, int W2, int H2) {
+    STRIPE_CHECK(M.size() == 6, "warp: a matrix is six numbers");
+    WarpSpec s;
+    for (int i = 0; i < 6; ++i) s.M[i] = M[(size_t)i];
+    return warp_token(s, W2, H2);
+  }, py::arg("M"), py::arg("W2"), py::arg("H2"), "the canonical token of a forward matrix and its destination size");
+  m.def("parse_warp_border", [](const std::string& token) {
+    WarpBorder b;
+    uint8_t fill;
+    parse_warp_border(token, &b, &fill);
+    return py::make_tuple(std::string(warp_border_name(b)), (int)fill);
+  }, py::arg("token"), "'constant[:V]' | 'replicate' -> (name, fill)");
+  m.def("parse_warp_mode", [](const std::string& token) { return std::string(warp_mode_name(parse_warp_mode(token))); },
+        py::arg("token"));
+  m.def("golden_warp", [](const U8Array& a, const std::vector<int64_t>& q, int W2, int H2, const std::string& mode,
+                          const std::string& border, int fill) {
+    const Image img = image_from_numpy(a);
+    const WarpMap wm = warp_map_from_py(q, W2, H2, mode, border, fill);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_warp(img, wm);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("map"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "bilinear",
+     py::arg("border") = "constant", py::arg("fill") = 0);
+  m.def("cpu_warp", [](const U8Array& a, const std::vector<int64_t>& q, int W2, int H2, const std::string& mode,
+                       const std::string& border, int fill, int threads) {
+    const Image img = image_from_numpy(a);
+    const WarpMap wm = warp_map_from_py(q, W2, H2, mode, border, fill);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_warp(img, wm, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("map"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "bilinear",
+     py::arg("border") = "constant", py::arg("fill") = 0, py::arg("threads") = 0);
+  m.def("warp_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int C, uintptr_t dst, int64_t dst_pitch,
+                          const std::vector<int64_t>& q, int W2, int H2, const std::string& mode,
+                          const std::string& border, int fill, uintptr_t stream) {
+    const WarpMap wm = warp_map_from_py(q, W2, H2, mode, border, fill);
+    py::gil_scoped_release nogil;
+    warp_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, C, reinterpret_cast<uint8_t*>(dst), dst_pitch,
+                wm, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("C"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("map"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "bilinear",
+     py::arg("border") = "constant", py::arg("fill") = 0, py::arg("stream") = 0,
+     "k_warp on pitched device buffers (any alignment), queued on the stream");
+  m.def("warp_tile", [] {
+    py::dict d;
+    d["tile"] = kWarpTile;
+    d["box"] = kWarpBox;
+    d["row_bytes_gray"] = warp_row_bytes(1);
+    d["row_bytes_rgb"] = warp_row_bytes(3);
+    d["lds_gray"] = warp_lds_bytes(1);
+    d["lds_rgb"] = warp_lds_bytes(3);
+    return d;
+  }, "k_warp's tile constants: destination pixels per tile side, source pixels per side of the staged box, "
+     "bytes of a staged row and LDS bytes of the staged instances (gray / RGB); the direct instances hold none");
+  m.def("warp_plan", [](const std::vector<int64_t>& q) {
+    const WarpMap wm = warp_map_from_py(q, 1, 1, "bilinear", "constant", 0);
+    return std::string(warp_plan_staged(wm) ? "staged" : "direct");
+  }, py::arg("map"), "'staged' | 'direct': the k_warp instance a quantised map takes");
 
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },

@@ -61,6 +61,16 @@ def main(argv=None) -> int:
                         "of a JPEG input, none for any other format); without it the stored pixels are used")
     r.add_argument("--crop", default=None, metavar="WxH+X+Y",
                    help="a window of the oriented frame, cut in the same pass")
+    w = r.add_mutually_exclusive_group()
+    w.add_argument("--rotate", default=None, metavar="DEG[:same|fit]",
+                   help="rotate the frame counter-clockwise about its centre, after --orient / --crop and before "
+                        "--resize (fit: the frame grows to hold the turn); use --rotate=-30 for a negative angle")
+    w.add_argument("--warp", default=None, metavar="a;b;c;d;e;f[:WxH]",
+                   help="warp the frame by the forward 2x3 matrix (source -> destination, like cv2.warpAffine); "
+                        "WxH: the destination size (default: the source's)")
+    r.add_argument("--warp-mode", default=None, choices=["bilinear", "nearest"])
+    r.add_argument("--warp-border", default=None, metavar="constant[:V]|replicate",
+                   help="taps outside the frame: the fill value V (default 0) or the clamped pixel")
     r.add_argument("--verbose", "-v", action="store_true", help="rank-prefixed progress log on stderr")
     c = sub.add_parser("convert", help="convert between image formats")
     c.add_argument("src")
@@ -94,6 +104,8 @@ def main(argv=None) -> int:
 
         backend = "local" if torch.cuda.is_available() else "host"
     img, oriented = _orient_input(a, img, backend != "host")
+    img, warped = _warp_input(a, img, backend != "host")
+    oriented = {**oriented, **warped}
     img, resized_from = _resize_input(a, img, backend != "host")
     t0 = time.perf_counter()
     log = utils.get_logger("cli", 0)
@@ -134,6 +146,38 @@ def _orient_input(a, img, on_gpu):
     return out, {"oriented": name, "cropped_from": [int(W), int(H)]}
 
 
+def _warp_input(a, img, on_gpu):
+    """--rotate DEG[:same|fit] or --warp a;b;c;d;e;f[:WxH] on the loaded frame: (frame, JSON members)."""
+    if not a.rotate and not a.warp:
+        if a.warp_mode or a.warp_border:
+            raise SystemExit("--warp-mode and --warp-border need --rotate or --warp")
+        return img, {}
+    import numpy as np
+
+    from . import ops
+    from ._native import C
+
+    H, W = img.shape[:2]
+    border, fill = C.parse_warp_border(a.warp_border or "constant")
+    kw = dict(mode=C.parse_warp_mode(a.warp_mode or "bilinear"), border=border, fill=fill)
+    x = np.ascontiguousarray(img)
+    if on_gpu:
+        import torch
+
+        x = torch.from_numpy(x).cuda()
+    if a.rotate:
+        deg, fit, token = C.parse_rotate_spec(a.rotate)
+        out = ops.rotate(x, deg, expand=fit, **kw)
+    else:
+        M, W2, H2 = C.parse_warp_spec(a.warp)
+        W2, H2 = W2 or W, H2 or H
+        token = C.warp_token(M, W2, H2)
+        out = ops.warp_affine(x, M, size=(H2, W2), **kw)
+    if on_gpu:
+        out = out.cpu().numpy()
+    return out, {"warped_from": [int(W), int(H)], "warp": token}
+
+
 def _resize_input(a, img, on_gpu):
     """--resize WxH[:mode] on the loaded frame: (frame, [W, H] it had, or None)."""
     if not a.resize:
@@ -169,6 +213,8 @@ def _run_per_process(a, pipe) -> int:
     oriented = {}
     if ctx.rank == 0:  # rank 0 orients, crops and resizes before it broadcasts the geometry
         img, oriented = _orient_input(a, img, a.backend in ("rccl", "gloo-gpu"))
+        img, warped = _warp_input(a, img, a.backend in ("rccl", "gloo-gpu"))
+        oriented = {**oriented, **warped}
         img, resized_from = _resize_input(a, img, a.backend in ("rccl", "gloo-gpu"))
     meta = [None if img is None else tuple(img.shape)]
     if ctx.world > 1:

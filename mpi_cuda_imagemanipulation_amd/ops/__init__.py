@@ -598,6 +598,128 @@ def exif_orientation(path_or_bytes) -> int:
     return C.jpeg_orientation(data)
 
 
+# ---- affine warp: a stage in front of the chain (after orient / crop, before resize) ----
+WARP_MODES = ("bilinear", "nearest")
+WARP_BORDERS = ("constant", "replicate")
+
+
+def _warp_map(W, H, M, size, inverse):
+    """The quantised map of a 2x3 matrix: ([A00, A01, B0, A10, A11, B1], W2, H2)."""
+    try:
+        vals = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError(f"M must be a 2x3 matrix of numbers, got {M!r}") from None
+    if len(vals) != 6:
+        raise ValueError(f"M must be a 2x3 matrix (six numbers), got {len(vals)}")
+    if size is None:
+        H2, W2 = H, W
+    else:
+        try:
+            H2, W2 = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"size must be (H2, W2), got {size!r}") from None
+    if not (1 <= W2 <= 65535 and 1 <= H2 <= 65535):
+        raise ValueError(f"warp: destination size {W2}x{H2} outside 1..65535")
+    try:
+        q = C.warp_quantise(vals, bool(inverse), W, H, W2, H2)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return list(q[:6]), q[6], q[7]
+
+
+def _warp_args(mode, border, fill):
+    if mode not in WARP_MODES:
+        raise ValueError(f"warp: unknown mode {mode!r} (bilinear | nearest)")
+    if border not in WARP_BORDERS:
+        raise ValueError(f"warp: unknown border {border!r} (constant | replicate)")
+    if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= 255:
+        raise ValueError(f"warp: fill must be an integer in 0..255, got {fill!r}")
+    return mode, border, int(fill)
+
+
+def _warp_frame(x, mapper, mode, border, fill):
+    """One frame (or a batch, frame by frame) through k_warp / cpu_warp; mapper(W, H) -> (q, W2, H2)."""
+    if x.ndim == 4:
+        if x.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
+        outs = [_warp_frame(x[b], mapper, mode, border, fill) for b in range(x.shape[0])]
+        if outs:
+            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
+        _, W2, H2 = mapper(x.shape[2], x.shape[1])
+        shape = (0, H2, W2, x.shape[3])
+        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
+    W, H, Cc = _shape(x)
+    q, W2, H2 = mapper(W, H)
+    if _is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        # the kernel takes pitched views: only the pixels of a row must be packed
+        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
+        xc = x if packed else x.contiguous()
+        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            C.warp_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, q, W2, H2, mode, border,
+                          fill, stream.cuda_stream)
+        # keep the input alive until the stream has consumed it
+        xc.record_stream(stream)
+        return out
+    was_tensor = _is_tensor(x)
+    arr = x.numpy() if was_tensor else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.cpu_warp(np.ascontiguousarray(arr[:, :, 0] if keep else arr), q, W2, H2, mode, border, fill)
+    if keep:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if was_tensor else out
+
+
+def warp_affine(x, M, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0,
+                inverse: bool = False):
+    """Affine warp by the forward 2x3 matrix M (source -> destination, like cv2.warpAffine without
+    WARP_INVERSE_MAP; inverse=True: M maps destination to source itself).
+
+    size=(H2, W2) is the destination (default: the source's).  Integer indices are pixel centres.  The
+    inverse map is quantised to Q24 once; every pixel follows from it in integers, so CUDA uint8 tensors
+    (the k_warp HIP kernel on torch's current stream; rows of a strided view are read in place), numpy
+    arrays / CPU tensors (the threaded host executor) and `warp_reference` agree bit for bit.  Taps
+    outside the frame are `fill` (border="constant") or the clamped pixel ("replicate").  A map that
+    shrinks is not antialiased.  A BxHxWxC batch runs frame by frame."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    return _warp_frame(x, lambda W, H: _warp_map(W, H, M, size, inverse), mode, border, fill)
+
+
+def _rotation_mapper(angle, expand):
+    def mapper(W, H):
+        try:
+            minv, W2, H2 = C.rotate_matrix(float(angle), bool(expand), W, H)
+        except RuntimeError as e:
+            raise ValueError(str(e)) from None
+        return _warp_map(W, H, minv, (H2, W2), True)
+    return mapper
+
+
+def rotate(x, angle: float, expand: bool = False, mode: str = "bilinear", border: str = "constant", fill: int = 0):
+    """Rotation by `angle` degrees, counter-clockwise as seen (cv2.getRotationMatrix2D, PIL), about the
+    frame's centre.  expand=True grows the frame to hold the whole rotated image (multiples of 90 are then
+    exact quarter turns); otherwise the size is kept.  See `warp_affine`."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    return _warp_frame(x, _rotation_mapper(angle, expand), mode, border, fill)
+
+
+def warp_reference(x, M, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0,
+                   inverse: bool = False):
+    """Golden CPU result of `warp_affine`: the rule as a plain per-pixel loop."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    W, H, _ = _shape(arr)
+    q, W2, H2 = _warp_map(W, H, M, size, inverse)
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.golden_warp(np.ascontiguousarray(arr[:, :, 0] if keep else arr), q, W2, H2, mode, border, fill)
+    return out[:, :, None] if keep else out
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -613,4 +735,5 @@ __all__ = [
     "combine", "absdiff", "add", "subtract", "blend", "minimum", "maximum",
     "resize", "resize_reference", "RESIZE_MODES",
     "orient", "orient_reference", "flip", "rot90", "transpose_image", "crop", "exif_orientation", "ORIENTATIONS",
+    "warp_affine", "rotate", "warp_reference", "WARP_MODES", "WARP_BORDERS",
 ]

@@ -50,6 +50,7 @@ CORE_SOURCES = [
     "core/cpu_exec.cpp",
     "core/resize.cpp",
     "core/orient.cpp",
+    "core/warp.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -65,6 +66,7 @@ CORE_SOURCES = [
     "hip/combine.hip",
     "hip/resize.hip",
     "hip/orient.hip",
+    "hip/warp.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
