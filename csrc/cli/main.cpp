@@ -21,6 +21,7 @@
 //   stripe gen   --synthetic WxHxC --seed S --output x.ppm
 //   stripe convert --input a.jpg --output b.ppm [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]
 //                  [--rotate DEG[:same|fit] | --warp "a;b;c;d;e;f[:WxH]"] [--warp-mode M] [--warp-border B]
+//                  [--perspective "h00;...;h22[:WxH]" | --quad "x0,y0;...;x3,y3[:WxH]" | --undistort "k1[;k2[;f[;cx;cy]]]"]
 //                  [--resize WxH[:mode]]
 //   stripe info  [--chain ...] [--channels C] [--format json]
 #include <hip/hip_runtime.h>
@@ -360,11 +361,71 @@ std::string orient_input(const Args& a, Input* in, const std::string& path, bool
 // the frame is warped after --orient / --crop and before --resize and the
 // chain: on the GPU (k_warp) for device backends, on cpu_warp for the host
 // backend.  `token` gets the canonical form of the request.
+//
+// --perspective "h00;...;h22[:WxH]" (the forward 3 x 3 matrix), --quad
+// "x0,y0;x1,y1;x2,y2;x3,y3[:WxH]" (TL TR BR BL of the source, straightened) and
+// --undistort "k1[;k2[;f[;cx;cy]]]" sit in the same slot and take the same mode
+// and border; they run as a mesh warp (stripe/remap.h): k_remap / cpu_remap.
+bool mesh_requested(const Args& a) { return a.has("perspective") || a.has("quad") || a.has("undistort"); }
+
 bool warp_requested(const Args& a) {
-  STRIPE_CHECK(!(a.has("rotate") && a.has("warp")), "--rotate and --warp are mutually exclusive");
-  STRIPE_CHECK(a.has("rotate") || a.has("warp") || (!a.has("warp-mode") && !a.has("warp-border")),
-               "--warp-mode and --warp-border need --rotate or --warp");
-  return a.has("rotate") || a.has("warp");
+  const int n = (int)a.has("rotate") + (int)a.has("warp") + (int)a.has("perspective") + (int)a.has("quad") +
+                (int)a.has("undistort");
+  STRIPE_CHECK(n <= 1, "--rotate, --warp, --perspective, --quad and --undistort are mutually exclusive");
+  STRIPE_CHECK(n == 1 || (!a.has("warp-mode") && !a.has("warp-border")),
+               "--warp-mode and --warp-border need --rotate or --warp (or --perspective, --quad, --undistort)");
+  return n == 1;
+}
+
+Mesh mesh_of(const Args& a, int W, int H, std::string* token) {
+  if (a.has("perspective")) {
+    const PerspectiveSpec p = parse_perspective_spec(a.get("perspective"));
+    const int W2 = p.W2 > 0 ? p.W2 : W, H2 = p.H2 > 0 ? p.H2 : H;
+    if (token) *token = perspective_token(p.Hm, W2, H2);
+    return perspective_mesh(p.Hm, false, W, H, W2, H2, 0, a.get("perspective"));
+  }
+  if (a.has("quad")) {
+    const QuadSpec q = parse_quad_spec(a.get("quad"));
+    double Hm[9];
+    quad_matrix(q.pts, q.W2, q.H2, Hm, a.get("quad"));
+    if (token) *token = quad_token(q.pts, q.W2, q.H2);
+    return perspective_mesh(Hm, false, W, H, q.W2, q.H2, 0, a.get("quad"));
+  }
+  const RadialSpec r = parse_undistort_spec(a.get("undistort"));
+  if (token) *token = undistort_token(radial_resolve(r, W, H));
+  return radial_mesh(r, W, H, 0, a.get("undistort"));
+}
+
+Image remap_image(const Image& in, const Mesh& me, const Args& a, bool on_device, int device) {
+  WarpBorder border;
+  uint8_t fill;
+  parse_warp_border(a.get("warp-border", "constant"), &border, &fill);
+  RemapMesh rm = me.view(parse_warp_mode(a.get("warp-mode", "bilinear")), border, fill);
+  if (!on_device) return cpu_remap(in, rm, cpu_threads());
+  HIP_CHECK(hipSetDevice(device));
+  Image out(me.W2, me.H2, in.C, NoInit{});
+  uint8_t *ds = nullptr, *dd = nullptr;
+  int32_t* dm = nullptr;
+  const size_t mesh_bytes = me.nodes.size() * sizeof(int32_t);
+  try {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dm), mesh_bytes));
+    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dm, me.nodes.data(), mesh_bytes, hipMemcpyHostToDevice));
+    rm.nodes = dm;
+    remap_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), rm, (int64_t)me.nodes.size(), nullptr);
+    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+  } catch (...) {
+    (void)hipFree(ds);
+    (void)hipFree(dd);
+    (void)hipFree(dm);
+    throw;
+  }
+  HIP_CHECK(hipFree(ds));
+  HIP_CHECK(hipFree(dd));
+  HIP_CHECK(hipFree(dm));
+  return out;
 }
 
 WarpMap warp_map_of(const Args& a, int W, int H, std::string* token) {
@@ -410,17 +471,27 @@ Image warp_image(const Image& in, const WarpMap& m, bool on_device, int device) 
 std::string warp_input(const Args& a, Input* in, bool on_device, int device) {
   if (!warp_requested(a)) return "";
   const int W0 = in->W, H0 = in->H;
-  std::string token;
-  const WarpMap m = warp_map_of(a, W0, H0, &token);
-  if (in->coefs) {
-    in->img = jpeg_pixels(std::move(in->jpeg));
-    in->jpeg = JpegCoefs{};
-    in->coefs = false;
+  std::string token, extra;
+  auto pixels = [&] {
+    if (in->coefs) {
+      in->img = jpeg_pixels(std::move(in->jpeg));
+      in->jpeg = JpegCoefs{};
+      in->coefs = false;
+    }
+  };
+  if (mesh_requested(a)) {
+    const Mesh me = mesh_of(a, W0, H0, &token);
+    pixels();
+    in->img = remap_image(in->img, me, a, on_device, device);
+    extra = ",\"mesh_spacing\":" + std::to_string(me.spacing());
+  } else {
+    const WarpMap m = warp_map_of(a, W0, H0, &token);
+    pixels();
+    in->img = warp_image(in->img, m, on_device, device);
   }
-  in->img = warp_image(in->img, m, on_device, device);
   in->W = in->img.W;
   in->H = in->img.H;
-  return ",\"warped_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "],\"warp\":\"" + token + "\"";
+  return ",\"warped_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "],\"warp\":\"" + token + "\"" + extra;
 }
 
 // One rank of a multi-process job: `stripe run --backend rccl --world N --rank r
@@ -502,8 +573,12 @@ int cmd_run(const Args& a) {
       const Orient hop = orient_of(a, a.get("held"));
       held = orient_image(held, hop, crop_of(a, hop, held.W, held.H), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     }
-    if (warp_requested(a))  // the held image gets the same warp
-      held = warp_image(held, warp_map_of(a, held.W, held.H, nullptr), !host_run, rdevs.empty() ? 0 : rdevs[0]);
+    if (warp_requested(a)) {  // the held image gets the same warp
+      if (mesh_requested(a))
+        held = remap_image(held, mesh_of(a, held.W, held.H, nullptr), a, !host_run, rdevs.empty() ? 0 : rdevs[0]);
+      else
+        held = warp_image(held, warp_map_of(a, held.W, held.H, nullptr), !host_run, rdevs.empty() ? 0 : rdevs[0]);
+    }
     if (a.has("resize"))  // the held image is resized the same way
       held = resize_image(held, parse_resize_spec(a.get("resize")), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
@@ -923,6 +998,9 @@ void usage() {
                "        [--warp-border constant[:V]|replicate]\n"
                "            (the frame, and --held's, rotated counter-clockwise about its centre or warped by the forward\n"
                "             2x3 matrix, after --orient / --crop and before --resize; fit: the frame grows to hold the turn)\n"
+               "        [--perspective \"h00;...;h22[:WxH]\" | --quad \"x0,y0;x1,y1;x2,y2;x3,y3[:WxH]\" | --undistort \"k1[;k2[;f[;cx;cy]]]\"]\n"
+               "            (in the same slot, with the same mode and border: the forward 3x3 matrix; the source quad TL TR BR BL\n"
+               "             straightened to a rectangle; radial lens undistortion, f default half the diagonal)\n"
                "        [--resize WxH[:auto|nearest|bilinear|area]]  (the frame, and --held's, resized before the chain)\n"
                "        one process per rank: --backend rccl --world N --rank r --rendezvous FILE [--device d]\n"
                "  bench --synthetic WxHxC [--seed S] [--chain C] [--ranks 1,2,4,8] [--iters N] [--warmup N]\n"
@@ -934,6 +1012,7 @@ void usage() {
                "  gen   --synthetic WxHxC [--seed S] --output out.ppm|out.jpg\n"
                "  convert --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95] [--orient OP|auto] [--crop WxH+X+Y]\n"
                "        [--rotate DEG[:same|fit] | --warp \"a;b;c;d;e;f[:WxH]\"] [--warp-mode M] [--warp-border B]\n"
+               "        [--perspective H | --quad Q | --undistort K]\n"
                "        [--resize WxH[:mode]] [--backend host]\n"
                "  info  [--chain C] [--channels C] [--format json]\n");
 }

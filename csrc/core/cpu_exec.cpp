@@ -13,6 +13,7 @@
 
 #include "stripe/orient.h"
 #include "stripe/rank_net.h"
+#include "stripe/remap.h"
 #include "stripe/resize.h"
 #include "stripe/warp.h"
 
@@ -822,6 +823,90 @@ Image cpu_warp(const Image& in, const WarpMap& m, int threads) {
                "warp: destination size " << m.W2 << "x" << m.H2 << " outside 1.." << kWarpMaxSize);
   Image out(m.W2, m.H2, in.C, NoInit{});
   cpu_warp(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), m, threads);
+  return out;
+}
+
+// ---- mesh warp (stripe/remap.h) ----
+namespace {
+template <int C, bool BIL>
+void remap_rows(const uint8_t* src, int64_t sp, int W, int H, uint8_t* dst, int64_t dp, const RemapMesh& m, int ya, int yb) {
+  const int s = m.shift, gw = m.gw();
+  const int64_t S = int64_t(1) << s;
+  const bool rep = m.border == WarpBorder::Replicate;
+  const uint32_t fill = m.fill;
+  const int sh = BIL ? 4 + 2 * s : 12 + 2 * s;
+  const int64_t rnd = int64_t(1) << (sh - 1);
+  auto tap = [&](int64_t iy, int64_t ix, int ch) -> uint32_t {
+    if (rep) {
+      iy = std::min<int64_t>(std::max<int64_t>(iy, 0), H - 1);
+      ix = std::min<int64_t>(std::max<int64_t>(ix, 0), W - 1);
+    } else if (ix < 0 || iy < 0 || ix >= W || iy >= H) {
+      return fill;
+    }
+    return src[iy * sp + ix * C + ch];
+  };
+  for (int y = ya; y < yb; ++y) {
+    const int i = y >> s;
+    const int64_t ty = y & (S - 1);
+    const int32_t* n0 = m.nodes + (size_t)i * gw * 2;
+    const int32_t* n1 = n0 + (size_t)gw * 2;
+    uint8_t* o = dst + (int64_t)y * dp;
+    for (int x0 = 0; x0 < m.W2; x0 += (int)S) {
+      const int j = x0 >> s;
+      // the cell's left and right edges at this row; P = S L + tx (R - L)
+      const int64_t Lx = (S - ty) * n0[2 * j] + ty * n1[2 * j], Rx = (S - ty) * n0[2 * j + 2] + ty * n1[2 * j + 2];
+      const int64_t Ly = (S - ty) * n0[2 * j + 1] + ty * n1[2 * j + 1], Ry = (S - ty) * n0[2 * j + 3] + ty * n1[2 * j + 3];
+      int64_t Px = S * Lx + rnd, Py = S * Ly + rnd;
+      const int64_t dx = Rx - Lx, dy = Ry - Ly;
+      const int xe = std::min<int64_t>(x0 + S, m.W2);
+      for (int x = x0; x < xe; ++x, Px += dx, Py += dy, o += C) {
+        if constexpr (BIL) {
+          const int64_t X = Px >> sh, Y = Py >> sh;
+          const int64_t ix = X >> 8, iy = Y >> 8;
+          const uint32_t fx = (uint32_t)(X & 255), fy = (uint32_t)(Y & 255);
+          if (ix >= 0 && iy >= 0 && ix + 1 < W && iy + 1 < H) {  // every tap inside the frame
+            const uint8_t* q = src + iy * sp + ix * C;
+            for (int ch = 0; ch < C; ++ch) o[ch] = (uint8_t)warp_bilinear(q[ch], q[C + ch], q[sp + ch], q[sp + C + ch], fx, fy);
+          } else {
+            for (int ch = 0; ch < C; ++ch)
+              o[ch] = (uint8_t)warp_bilinear(tap(iy, ix, ch), tap(iy, ix + 1, ch), tap(iy + 1, ix, ch),
+                                             tap(iy + 1, ix + 1, ch), fx, fy);
+          }
+        } else {
+          const int64_t ix = Px >> sh, iy = Py >> sh;
+          for (int ch = 0; ch < C; ++ch) o[ch] = (uint8_t)tap(iy, ix, ch);
+        }
+      }
+    }
+  }
+}
+}  // namespace
+
+void cpu_remap(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
+               const RemapMesh& m, int threads) {
+  STRIPE_CHECK(C == 1 || C == 3, "remap: image must have 1 or 3 channels, got C = " << C);
+  STRIPE_CHECK(src && dst, "remap: empty image");
+  STRIPE_CHECK(W >= 1 && H >= 1 && W <= kWarpMaxSize && H <= kWarpMaxSize,
+               "remap: source size " << W << "x" << H << " outside 1.." << kWarpMaxSize);
+  check_mesh(m, (int64_t)m.gh() * m.gw() * 2, true);
+  STRIPE_CHECK(src_pitch >= (int64_t)W * C && dst_pitch >= (int64_t)m.W2 * C, "remap: pitch smaller than a row");
+  const bool bil = m.mode == WarpMode::Bilinear;
+  parallel_rows(0, m.H2, (bil ? 6 : 3) * (int64_t)m.W2 * C, std::max(1, threads), [&](int ya, int yb) {
+    if (C == 1) {
+      if (bil) remap_rows<1, true>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+      else remap_rows<1, false>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+    } else {
+      if (bil) remap_rows<3, true>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+      else remap_rows<3, false>(src, src_pitch, W, H, dst, dst_pitch, m, ya, yb);
+    }
+  });
+}
+
+Image cpu_remap(const Image& in, const RemapMesh& m, int threads) {
+  STRIPE_CHECK(in.C == 1 || in.C == 3, "remap: image must have 1 or 3 channels, got C = " << in.C);
+  check_mesh(m, (int64_t)m.gh() * m.gw() * 2, true);
+  Image out(m.W2, m.H2, in.C, NoInit{});
+  cpu_remap(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), m, threads);
   return out;
 }
 

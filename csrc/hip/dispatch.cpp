@@ -193,6 +193,30 @@ void launch_warp(const WarpLaunch& L, hipStream_t s) {
   launch_warp_kernel(L, s);
 }
 
+void launch_remap(const RemapLaunch& L, hipStream_t s) {
+  // host-side shape checks before the kernel touches memory (the nodes themselves stay on the device: the
+  // kernel clamps or tests every index that follows from them)
+  STRIPE_CHECK(L.src && L.dst, "bad remap launch: null src or dst");
+  STRIPE_CHECK(L.C == 1 || L.C == 3, "remap needs 1 or 3 channels, got C = " << L.C);
+  STRIPE_CHECK(L.W >= 1 && L.W <= kWarpMaxSize && L.H >= 1 && L.H <= kWarpMaxSize,
+               "remap: source size " << L.W << "x" << L.H << " outside 1.." << kWarpMaxSize);
+  const RemapMesh& m = L.mesh;
+  check_mesh(m, L.mesh_count, false, "launch");
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "remap: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)m.W2 * L.C, "remap: dst_pitch " << L.dst_pitch << " < row bytes " << m.W2 * L.C);
+  STRIPE_CHECK((reinterpret_cast<uintptr_t>(m.nodes) & 3) == 0, "remap: the mesh must be aligned to 4 bytes");
+  if (L.src_base)
+    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
+                                            L.src_bytes,
+                 "remap: source rows outside their buffer");
+  if (L.dst_base)
+    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(m.H2 - 1) * L.dst_pitch +
+                                                (int64_t)m.W2 * L.C <= L.dst_bytes,
+                 "remap: destination rows outside their buffer");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_remap_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

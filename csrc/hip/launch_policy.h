@@ -181,6 +181,7 @@ enum class Family {
   Resize,         // k_resize
   Orient,         // k_orient
   Warp,           // k_warp
+  Remap,          // k_remap
 };
 
 struct PolicyIn {
@@ -191,7 +192,8 @@ struct PolicyIn {
   int wgs = -1;                     // PassLaunch::wgs
   bool gray_prologue = false;       // stencil with a gray prologue (3 input bytes per output byte)
   bool lut_stage = false;           // colour matrix with a pre or post LUT stage
-  int W2 = 0, rows2 = 0;            // resize, warp: pixels per row and rows of the destination (W, rows: the source)
+  int W2 = 0, rows2 = 0;            // resize, warp, remap: pixels per row and rows of the destination (W, rows: the source)
+  int64_t mesh_bytes = 0;           // remap: bytes of the mesh
 };
 
 struct StreamPolicy {
@@ -229,7 +231,7 @@ constexpr int stencil_cap_default(Family f, bool gray_prologue) {
 //   * all pointwise families and k_conv_small ignore PassLaunch::nt;
 //   * channel-changing pointwise applies its cap by size, whatever nt is;
 //   * the MFMA blur does not read STRIPE_NT;
-//   * resize, orient and warp have no occupancy cap and ignore PassLaunch::nt / wgs.
+//   * resize, orient, warp and remap have no occupancy cap and ignore PassLaunch::nt / wgs.
 inline StreamPolicy stream_policy(const PolicyIn& in) {
   StreamPolicy r;
   const int64_t px = (int64_t)in.rows * in.W;
@@ -328,6 +330,13 @@ inline StreamPolicy stream_policy(const PolicyIn& in) {
       // the orient family's rule on the pixels of both frames: at most one read of the source
       // (W x rows) and one write of the destination (W2 x rows2), cin channels each
       r.streaming = (px + (int64_t)in.rows2 * in.W2) * in.cin > dev::kNtMinBytes;
+      r.nt_stores = r.streaming;
+      if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
+      break;
+    }
+    case Family::Remap: {
+      // the warp family's rule with the mesh bytes (read once) added to source + destination
+      r.streaming = (px + (int64_t)in.rows2 * in.W2) * in.cin + in.mesh_bytes > dev::kNtMinBytes;
       r.nt_stores = r.streaming;
       if (const int e = env_nt(); e >= 0) r.nt_stores = e != 0;  // overrides either way
       break;

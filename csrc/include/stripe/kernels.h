@@ -12,6 +12,7 @@
 #include "stripe/chain.h"
 #include "stripe/image.h"
 #include "stripe/orient.h"
+#include "stripe/remap.h"
 #include "stripe/resize.h"
 #include "stripe/warp.h"
 
@@ -261,6 +262,44 @@ void launch_warp(const WarpLaunch& L, hipStream_t s);         // dispatch.cpp: c
 void launch_warp_kernel(const WarpLaunch& L, hipStream_t s);  // warp.hip
 void warp_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
                  const WarpMap& map, hipStream_t s);
+
+// Mesh warp of a whole frame (csrc/hip/remap.hip k_remap; the rule:
+// stripe/remap.h).  Addressing as k_warp.  The mesh lives on the device; the
+// host never reads it, so the kernel decides per tile:
+//   * spacing >= kRemapLdsSpacing: the tile's nodes (at most kRemapNodes a
+//     side) go to LDS and their minimum and maximum bound the tile's source box
+//     (a bilinear patch lies in the hull of its nodes).  A box of at most
+//     kWarpBox pixels a side is staged in LDS with k_warp's loads and gathered
+//     with coordinates relative to it (32 bits); a larger one gathers from
+//     global memory in int64, for that tile alone (a workgroup-uniform branch).
+//     A box that misses the frame under `constant` stores the fill byte.
+//   * smaller spacings: nodes from global memory per pixel, taps from global
+//     memory.
+// Every node index is clamped to the mesh and every tap clamped or tested, so
+// no mesh, whatever it holds, reads outside the frame.
+constexpr int kRemapLdsSpacing = 4;
+constexpr int kRemapNodes = kWarpTile / kRemapLdsSpacing + 1;  // 17
+constexpr int remap_node_bytes() { return kRemapNodes * kRemapNodes * 2 * 4; }
+constexpr int kRemapReduceBytes = 4 * 4 * 4;  // four waves' minima and maxima
+constexpr int remap_lds_bytes(int C) { return warp_lds_bytes(C) + remap_node_bytes() + kRemapReduceBytes; }
+struct RemapLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int W = 0, H = 0, C = 0;  // the source, pixels
+  uint8_t* dst = nullptr;   // mesh.W2 x mesh.H2 pixels
+  int64_t dst_pitch = 0;
+  RemapMesh mesh;           // nodes: device memory
+  int64_t mesh_count = 0;   // int32 values behind mesh.nodes
+  // optional: the allocations the views lie in (checked against the rows touched)
+  const uint8_t* src_base = nullptr;
+  int64_t src_bytes = 0;
+  const uint8_t* dst_base = nullptr;
+  int64_t dst_bytes = 0;
+};
+void launch_remap(const RemapLaunch& L, hipStream_t s);         // dispatch.cpp: checks, then the kernel
+void launch_remap_kernel(const RemapLaunch& L, hipStream_t s);  // remap.hip
+void remap_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
+                  const RemapMesh& mesh, int64_t mesh_count, hipStream_t s);
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

@@ -312,7 +312,7 @@ PYBIND11_MODULE(_C, m) {
 
   // ---- launch policy (csrc/hip/launch_policy.h: pure host functions, no GPU) ----
   m.def("launch_policy", [](const std::string& family, int cin, int cout, int cmid, int W, int rows, int nt, int wgs,
-                            bool gray_prologue, bool lut_stage, int W2, int rows2) {
+                            bool gray_prologue, bool lut_stage, int W2, int rows2, int64_t mesh_bytes) {
     static const std::pair<const char*, policy::Family> names[] = {
         {"sep", policy::Family::Sep},           {"sobel_rp", policy::Family::SobelRp},
         {"direct", policy::Family::Direct},     {"rank", policy::Family::Rank},
@@ -321,7 +321,7 @@ PYBIND11_MODULE(_C, m) {
         {"pointwise_flat", policy::Family::PointwiseFlat}, {"colormix", policy::Family::ColorMix},
         {"blur", policy::Family::Blur},         {"combine", policy::Family::Combine},
         {"resize", policy::Family::Resize},     {"orient", policy::Family::Orient},
-        {"warp", policy::Family::Warp}};
+        {"warp", policy::Family::Warp},         {"remap", policy::Family::Remap}};
     const policy::Family* f = nullptr;
     for (const auto& n : names)
       if (family == n.first) f = &n.second;
@@ -338,6 +338,7 @@ PYBIND11_MODULE(_C, m) {
     in.lut_stage = lut_stage;
     in.W2 = W2;
     in.rows2 = rows2;
+    in.mesh_bytes = mesh_bytes;
     const policy::StreamPolicy r = policy::stream_policy(in);
     py::dict d;
     d["nt_stores"] = r.nt_stores;
@@ -348,10 +349,11 @@ PYBIND11_MODULE(_C, m) {
     return d;
   }, py::arg("family"), py::arg("cin") = 3, py::arg("cout") = 3, py::arg("cmid") = 3, py::arg("W") = 0,
      py::arg("rows") = 0, py::arg("nt") = -1, py::arg("wgs") = -1, py::arg("gray_prologue") = false,
-     py::arg("lut_stage") = false, py::arg("W2") = 0, py::arg("rows2") = 0,
+     py::arg("lut_stage") = false, py::arg("W2") = 0, py::arg("rows2") = 0, py::arg("mesh_bytes") = 0,
      "the launch decision of a kernel family: sep | sobel_rp | direct | rank | bilateral | conv_small | pointwise | "
      "pointwise_flat | colormix | blur | combine | resize (W2, rows2: the destination of a resize) | orient (W, rows: "
-     "the source window) | warp (W, rows: the source; W2, rows2: the destination)");
+     "the source window) | warp (W, rows: the source; W2, rows2: the destination) | remap (as warp; mesh_bytes: the "
+     "bytes of the mesh)");
   m.def("lds_reserve_bytes", &policy::lds_reserve_bytes, py::arg("lds_per_cu"), py::arg("static_lds"),
         py::arg("target"));
 
@@ -640,6 +642,154 @@ PYBIND11_MODULE(_C, m) {
     const WarpMap wm = warp_map_from_py(q, 1, 1, "bilinear", "constant", 0);
     return std::string(warp_plan_staged(wm) ? "staged" : "direct");
   }, py::arg("map"), "'staged' | 'direct': the k_warp instance a quantised map takes");
+
+  // ---- mesh warp (stripe/remap.h): perspective, undistort, remap; in the affine warp's slot ----
+  // A mesh travels as an int32 array of shape (gh, gw, 2) with its spacing.
+  using MeshArray = py::array_t<int32_t, py::array::c_style>;
+  static const auto mesh_to_numpy = [](const Mesh& me) {
+    MeshArray out({(py::ssize_t)me.gh(), (py::ssize_t)me.gw(), (py::ssize_t)2});
+    std::memcpy(out.mutable_data(), me.nodes.data(), me.nodes.size() * sizeof(int32_t));
+    return py::make_tuple(out, me.spacing());
+  };
+  static const auto remap_view = [](const int32_t* nodes, int spacing, int W2, int H2, const std::string& mode,
+                                    const std::string& border, int fill) {
+    STRIPE_CHECK(fill >= 0 && fill <= 255, "remap: the fill value must be in 0..255, got " << fill);
+    RemapMesh rm;
+    rm.nodes = nodes;
+    rm.shift = remap_shift(spacing);
+    rm.W2 = W2, rm.H2 = H2;
+    rm.mode = parse_warp_mode(mode);
+    if (border == "constant") rm.border = WarpBorder::Constant, rm.fill = (uint8_t)fill;
+    else if (border == "replicate") rm.border = WarpBorder::Replicate;
+    else fail("warp: unknown border '" + border + "' (constant | replicate)");
+    return rm;
+  };
+  static const auto mesh_from_numpy = [](const py::array& mesh, int spacing, int W2, int H2, const std::string& mode,
+                                         const std::string& border, int fill, MeshArray* keep) {
+    STRIPE_CHECK(py::isinstance<py::array_t<int32_t>>(mesh), "remap 'mesh': the mesh must be an int32 array");
+    *keep = MeshArray::ensure(mesh);
+    STRIPE_CHECK(*keep, "remap 'mesh': the mesh must be an int32 array");
+    RemapMesh rm = remap_view(keep->data(), spacing, W2, H2, mode, border, fill);
+    STRIPE_CHECK(W2 >= 1 && W2 <= kWarpMaxSize && H2 >= 1 && H2 <= kWarpMaxSize,
+                 "remap 'mesh': destination size " << W2 << "x" << H2 << " outside 1.." << kWarpMaxSize);
+    STRIPE_CHECK(keep->ndim() == 3 && keep->shape(0) == rm.gh() && keep->shape(1) == rm.gw() && keep->shape(2) == 2,
+                 "remap 'mesh': a mesh of spacing " << spacing << " for " << W2 << "x" << H2 << " has shape " << rm.gh()
+                                                    << "x" << rm.gw() << "x2");
+    check_mesh(rm, (int64_t)keep->size(), true);
+    return rm;
+  };
+  m.def("perspective_mesh", [](const std::vector<double>& Hm, bool inverse, int W, int H, int W2, int H2, int spacing,
+                               const std::string& token) {
+    STRIPE_CHECK(Hm.size() == 9, "remap '" << token << "': a matrix is nine numbers (row-major 3 x 3), got " << Hm.size());
+    return mesh_to_numpy(perspective_mesh(Hm.data(), inverse, W, H, W2 > 0 ? W2 : W, H2 > 0 ? H2 : H, spacing, token));
+  }, py::arg("H"), py::arg("inverse") = false, py::arg("W") = 1, py::arg("Hs") = 1, py::arg("W2") = 0,
+     py::arg("H2") = 0, py::arg("spacing") = 0, py::arg("token") = "perspective",
+     "(int32 mesh (gh, gw, 2), spacing) of the forward (or, inverse=True, the inverse) 3 x 3 matrix for a W x Hs "
+     "source; W2, H2 = 0: the source's size; spacing 0: automatic");
+  m.def("radial_mesh", [](double k1, double k2, py::object f, py::object centre, int W, int H, int spacing,
+                          const std::string& token) {
+    RadialSpec r;
+    r.k1 = k1, r.k2 = k2;
+    if (!f.is_none()) r.has_f = true, r.f = f.cast<double>();
+    if (!centre.is_none()) {
+      const auto c = centre.cast<std::vector<double>>();
+      STRIPE_CHECK(c.size() == 2, "remap '" << token << "': the centre is (cx, cy)");
+      r.has_centre = true, r.cx = c[0], r.cy = c[1];
+    }
+    return mesh_to_numpy(radial_mesh(r, W, H, spacing, token));
+  }, py::arg("k1"), py::arg("k2") = 0.0, py::arg("f") = py::none(), py::arg("centre") = py::none(), py::arg("W") = 1,
+     py::arg("H") = 1, py::arg("spacing") = 0, py::arg("token") = "undistort",
+     "(int32 mesh, spacing) of the radial undistortion map of a W x H frame");
+  m.def("perspective_from_points", [](const std::vector<double>& src, const std::vector<double>& dst) {
+    STRIPE_CHECK(src.size() == 8 && dst.size() == 8, "remap 'points': four points x, y each for source and destination");
+    std::vector<double> Hm(9);
+    perspective_from_points(src.data(), dst.data(), Hm.data());
+    return Hm;
+  }, py::arg("src"), py::arg("dst"), "cv::getPerspectiveTransform: the forward matrix, row-major");
+  m.def("parse_quad_spec", [](const std::string& spec) {
+    const QuadSpec q = parse_quad_spec(spec);
+    return py::make_tuple(std::vector<double>(q.pts, q.pts + 8), q.W2, q.H2);
+  }, py::arg("spec"), "'x0,y0;x1,y1;x2,y2;x3,y3[:WxH]' -> (points TL TR BR BL, W2, H2), the default size resolved");
+  m.def("quad_matrix", [](const std::vector<double>& pts, int W2, int H2) {
+    STRIPE_CHECK(pts.size() == 8, "remap 'quad': four points x, y each");
+    if (W2 <= 0 || H2 <= 0) quad_default_size(pts.data(), &W2, &H2);
+    std::vector<double> Hm(9);
+    quad_matrix(pts.data(), W2, H2, Hm.data());
+    return py::make_tuple(Hm, W2, H2);
+  }, py::arg("points"), py::arg("W2") = 0, py::arg("H2") = 0,
+     "(forward matrix, W2, H2) that maps the quad TL TR BR BL to the destination's corners");
+  m.def("parse_perspective_spec", [](const std::string& spec) {
+    const PerspectiveSpec p = parse_perspective_spec(spec);
+    return py::make_tuple(std::vector<double>(p.Hm, p.Hm + 9), p.W2, p.H2);
+  }, py::arg("spec"), "'h00;...;h22[:WxH]' -> (forward matrix, W2, H2); 0, 0 without a size");
+  m.def("parse_undistort_spec", [](const std::string& spec) {
+    const RadialSpec r = parse_undistort_spec(spec);
+    return py::make_tuple(r.k1, r.k2, r.has_f ? py::object(py::float_(r.f)) : py::object(py::none()),
+                          r.has_centre ? py::object(py::make_tuple(r.cx, r.cy)) : py::object(py::none()));
+  }, py::arg("spec"), "'k1[;k2[;f[;cx;cy]]]' -> (k1, k2, f | None, (cx, cy) | None)");
+  m.def("perspective_token", [](const std::vector<double>& Hm, int W2, int H2) {
+    STRIPE_CHECK(Hm.size() == 9, "remap: a matrix is nine numbers");
+    return perspective_token(Hm.data(), W2, H2);
+  }, py::arg("H"), py::arg("W2"), py::arg("H2"), "the canonical token of a forward matrix and its destination size");
+  m.def("quad_token", [](const std::vector<double>& pts, int W2, int H2) {
+    STRIPE_CHECK(pts.size() == 8, "remap: a quad is four points");
+    return quad_token(pts.data(), W2, H2);
+  }, py::arg("points"), py::arg("W2"), py::arg("H2"));
+  m.def("undistort_token", [](const std::string& spec, int W, int H) {
+    return undistort_token(radial_resolve(parse_undistort_spec(spec), W, H));
+  }, py::arg("spec"), py::arg("W"), py::arg("H"), "the canonical token of an undistort spec for a W x H frame");
+  m.def("golden_remap", [](const U8Array& a, const py::array& mesh, int spacing, int W2, int H2, const std::string& mode,
+                           const std::string& border, int fill) {
+    const Image img = image_from_numpy(a);
+    MeshArray keep;
+    const RemapMesh rm = mesh_from_numpy(mesh, spacing, W2, H2, mode, border, fill, &keep);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_remap(img, rm);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("mesh"), py::arg("spacing"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "bilinear",
+     py::arg("border") = "constant", py::arg("fill") = 0);
+  m.def("cpu_remap", [](const U8Array& a, const py::array& mesh, int spacing, int W2, int H2, const std::string& mode,
+                        const std::string& border, int fill, int threads) {
+    const Image img = image_from_numpy(a);
+    MeshArray keep;
+    const RemapMesh rm = mesh_from_numpy(mesh, spacing, W2, H2, mode, border, fill, &keep);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_remap(img, rm, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("mesh"), py::arg("spacing"), py::arg("W2"), py::arg("H2"), py::arg("mode") = "bilinear",
+     py::arg("border") = "constant", py::arg("fill") = 0, py::arg("threads") = 0);
+  m.def("remap_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int C, uintptr_t dst, int64_t dst_pitch,
+                           uintptr_t mesh, int64_t mesh_count, int spacing, int W2, int H2, const std::string& mode,
+                           const std::string& border, int fill, uintptr_t stream) {
+    STRIPE_CHECK(mesh != 0, "bad remap launch: null mesh");
+    const RemapMesh rm = remap_view(reinterpret_cast<const int32_t*>(mesh), spacing, W2, H2, mode, border, fill);
+    py::gil_scoped_release nogil;
+    remap_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, C, reinterpret_cast<uint8_t*>(dst), dst_pitch,
+                 rm, mesh_count, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("C"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("mesh"), py::arg("mesh_count"), py::arg("spacing"), py::arg("W2"), py::arg("H2"),
+     py::arg("mode") = "bilinear", py::arg("border") = "constant", py::arg("fill") = 0, py::arg("stream") = 0,
+     "k_remap on pitched device buffers (any alignment) with a device-resident int32 mesh of mesh_count values, "
+     "queued on the stream");
+  m.def("remap_tile", [] {
+    py::dict d;
+    d["tile"] = kWarpTile;
+    d["box"] = kWarpBox;
+    d["lds_spacing"] = kRemapLdsSpacing;
+    d["nodes"] = kRemapNodes;
+    d["node_bytes"] = remap_node_bytes();
+    d["reduce_bytes"] = kRemapReduceBytes;
+    d["lds_gray"] = remap_lds_bytes(1);
+    d["lds_rgb"] = remap_lds_bytes(3);
+    return d;
+  }, "k_remap's tile constants: destination pixels per tile side, source pixels per side of the staged box, the "
+     "smallest spacing whose nodes go to LDS, nodes per tile side, their bytes, and the LDS bytes of an instance");
 
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },

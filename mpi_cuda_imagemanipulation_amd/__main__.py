@@ -68,6 +68,14 @@ def main(argv=None) -> int:
     w.add_argument("--warp", default=None, metavar="a;b;c;d;e;f[:WxH]",
                    help="warp the frame by the forward 2x3 matrix (source -> destination, like cv2.warpAffine); "
                         "WxH: the destination size (default: the source's)")
+    w.add_argument("--perspective", default=None, metavar="h00;...;h22[:WxH]",
+                   help="warp the frame by the forward 3x3 matrix (source -> destination, like cv2.warpPerspective), in "
+                        "the slot of --rotate / --warp")
+    w.add_argument("--quad", default=None, metavar="x0,y0;x1,y1;x2,y2;x3,y3[:WxH]",
+                   help="straighten the source quadrilateral TL TR BR BL to a rectangle (default size: its longer sides)")
+    w.add_argument("--undistort", default=None, metavar="k1[;k2[;f[;cx;cy]]]",
+                   help="radial lens undistortion (f default: half the diagonal; centre default: the frame's); use "
+                        "--undistort=-0.1 for a negative k1")
     r.add_argument("--warp-mode", default=None, choices=["bilinear", "nearest"])
     r.add_argument("--warp-border", default=None, metavar="constant[:V]|replicate",
                    help="taps outside the frame: the fill value V (default 0) or the clamped pixel")
@@ -147,10 +155,12 @@ def _orient_input(a, img, on_gpu):
 
 
 def _warp_input(a, img, on_gpu):
-    """--rotate DEG[:same|fit] or --warp a;b;c;d;e;f[:WxH] on the loaded frame: (frame, JSON members)."""
-    if not a.rotate and not a.warp:
+    """--rotate DEG[:same|fit], --warp a;b;c;d;e;f[:WxH], --perspective, --quad or --undistort on the loaded frame:
+    (frame, JSON members)."""
+    if not (a.rotate or a.warp or a.perspective or a.quad or a.undistort):
         if a.warp_mode or a.warp_border:
-            raise SystemExit("--warp-mode and --warp-border need --rotate or --warp")
+            raise SystemExit("--warp-mode and --warp-border need --rotate or --warp (or --perspective, --quad, "
+                             "--undistort)")
         return img, {}
     import numpy as np
 
@@ -165,7 +175,26 @@ def _warp_input(a, img, on_gpu):
         import torch
 
         x = torch.from_numpy(x).cuda()
-    if a.rotate:
+    extra = {}
+    if a.perspective or a.quad or a.undistort:
+        # the mesh is built here so that its spacing can be reported; ops.mesh_warp runs it
+        if a.perspective:
+            Hm, W2, H2 = C.parse_perspective_spec(a.perspective)
+            W2, H2 = W2 or W, H2 or H
+            token = C.perspective_token(Hm, W2, H2)
+            mesh, spacing = C.perspective_mesh(Hm, False, W, H, W2, H2, 0, a.perspective)
+        elif a.quad:
+            pts, W2, H2 = C.parse_quad_spec(a.quad)
+            token = C.quad_token(pts, W2, H2)
+            mesh, spacing = C.perspective_mesh(C.quad_matrix(pts, W2, H2)[0], False, W, H, W2, H2, 0, a.quad)
+        else:
+            k1, k2, f, centre = C.parse_undistort_spec(a.undistort)
+            W2, H2 = W, H
+            token = C.undistort_token(a.undistort, W, H)
+            mesh, spacing = C.radial_mesh(k1, k2, f, centre, W, H, 0, a.undistort)
+        out = ops.mesh_warp(x, mesh, spacing, size=(H2, W2), **kw)
+        extra = {"mesh_spacing": int(spacing)}
+    elif a.rotate:
         deg, fit, token = C.parse_rotate_spec(a.rotate)
         out = ops.rotate(x, deg, expand=fit, **kw)
     else:
@@ -175,7 +204,7 @@ def _warp_input(a, img, on_gpu):
         out = ops.warp_affine(x, M, size=(H2, W2), **kw)
     if on_gpu:
         out = out.cpu().numpy()
-    return out, {"warped_from": [int(W), int(H)], "warp": token}
+    return out, {"warped_from": [int(W), int(H)], "warp": token, **extra}
 
 
 def _resize_input(a, img, on_gpu):

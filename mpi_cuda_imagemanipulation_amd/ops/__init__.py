@@ -720,6 +720,265 @@ def warp_reference(x, M, size=None, mode: str = "bilinear", border: str = "const
     return out[:, :, None] if keep else out
 
 
+# ---- mesh warp: perspective, undistort, remap (the affine warp's slot in front of the chain) ----
+MESH_SPACINGS = (1, 2, 4, 8, 16, 32, 64)
+_NODE_LIMIT = 1 << 30  # 2^18 pixels in Q12
+
+
+def _mesh_grid(n, spacing):
+    return ((n - 1) >> (spacing.bit_length() - 1)) + 2
+
+
+def _check_spacing(spacing):
+    if isinstance(spacing, bool) or spacing not in MESH_SPACINGS:
+        raise ValueError(f"remap: spacing {spacing!r} is not a power of two in 1..64")
+    return int(spacing)
+
+
+def _dest_size(size, W, H):
+    if size is None:
+        return W, H
+    try:
+        H2, W2 = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H2, W2), got {size!r}") from None
+    if not (1 <= W2 <= 65535 and 1 <= H2 <= 65535):
+        raise ValueError(f"remap: destination size {W2}x{H2} outside 1..65535")
+    return W2, H2
+
+
+def _check_mesh(mesh, spacing, W2, H2):
+    """An int32 mesh of shape (gh, gw, 2) with every node inside (-2^18, 2^18) pixels; numpy or tensor."""
+    want = (_mesh_grid(H2, spacing), _mesh_grid(W2, spacing), 2)
+    if _is_tensor(mesh):
+        if mesh.dtype != torch.int32:
+            raise TypeError("the mesh must be int32")
+        if tuple(mesh.shape) != want:
+            raise ValueError(f"remap: a mesh of spacing {spacing} for {W2}x{H2} has shape "
+                             f"{want[0]}x{want[1]}x2, got {tuple(mesh.shape)}")
+        if mesh.numel() and int(mesh.abs().max()) >= _NODE_LIMIT:  # (int32 min wraps to itself: negative, caught below)
+            raise ValueError("remap: a node lies at or beyond 2^18 pixels")
+        if mesh.numel() and int(mesh.min()) <= -_NODE_LIMIT:
+            raise ValueError("remap: a node lies at or beyond 2^18 pixels")
+        return mesh.contiguous()
+    mesh = np.asarray(mesh)
+    if mesh.dtype != np.int32:
+        raise TypeError("the mesh must be int32")
+    if mesh.shape != want:
+        raise ValueError(f"remap: a mesh of spacing {spacing} for {W2}x{H2} has shape "
+                         f"{want[0]}x{want[1]}x2, got {mesh.shape}")
+    if mesh.size and (int(mesh.max()) >= _NODE_LIMIT or int(mesh.min()) <= -_NODE_LIMIT):
+        raise ValueError("remap: a node lies at or beyond 2^18 pixels")
+    return np.ascontiguousarray(mesh)
+
+
+def _remap_frame(x, mesher, mode, border, fill):
+    """One frame (or a batch, frame by frame) through k_remap / cpu_remap; mesher(W, H) -> (mesh, spacing,
+    W2, H2), the mesh a checked int32 array or tensor."""
+    if x.ndim == 4:
+        if x.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
+        outs = [_remap_frame(x[b], mesher, mode, border, fill) for b in range(x.shape[0])]
+        if outs:
+            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
+        _, _, W2, H2 = mesher(x.shape[2], x.shape[1])
+        shape = (0, H2, W2, x.shape[3])
+        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
+    W, H, Cc = _shape(x)
+    mesh, spacing, W2, H2 = mesher(W, H)
+    if _is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        # the kernel takes pitched views: only the pixels of a row must be packed
+        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
+        xc = x if packed else x.contiguous()
+        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            if _is_tensor(mesh):
+                dm = mesh.to(x.device).contiguous()
+            else:
+                dm = torch.from_numpy(mesh).to(x.device, non_blocking=False)
+            C.remap_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, dm.data_ptr(), dm.numel(),
+                           spacing, W2, H2, mode, border, fill, stream.cuda_stream)
+        # keep the input and the mesh alive until the stream has consumed them
+        xc.record_stream(stream)
+        dm.record_stream(stream)
+        return out
+    was_tensor = _is_tensor(x)
+    arr = x.numpy() if was_tensor else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    hm = mesh.cpu().numpy() if _is_tensor(mesh) else mesh
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = C.cpu_remap(np.ascontiguousarray(arr[:, :, 0] if keep else arr), hm, spacing, W2, H2, mode, border, fill)
+    if keep:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if was_tensor else out
+
+
+def _builder(fn, *args):
+    try:
+        return fn(*args)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+
+
+def _matrix9(Hm):
+    try:
+        vals = [float(v) for v in np.asarray(Hm, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError(f"H must be a 3x3 matrix of numbers, got {Hm!r}") from None
+    if len(vals) != 9:
+        raise ValueError(f"H must be a 3x3 matrix (nine numbers), got {len(vals)}")
+    return vals
+
+
+def _perspective_mesher(Hm, size, inverse):
+    vals = _matrix9(Hm)
+
+    def mesher(W, H):
+        W2, H2 = _dest_size(size, W, H)
+        mesh, s = _builder(C.perspective_mesh, vals, bool(inverse), W, H, W2, H2, 0)
+        return mesh, s, W2, H2
+    return mesher
+
+
+def mesh_warp(x, mesh, spacing: int, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0):
+    """Warp by a mesh: an int32 array or tensor of shape (gh, gw, 2) that holds the source position (x, y) in
+    Q12 of the destination pixels (j * spacing, i * spacing), gw = ((W2 - 1) // spacing) + 2, gh likewise;
+    between the nodes the position is interpolated bilinearly, in integers (`remap.h`).  size=(H2, W2) is the
+    destination (default: the source's).  CUDA uint8 tensors run the k_remap HIP kernel on torch's current
+    stream (a CUDA mesh is used where it lives), numpy arrays / CPU tensors the threaded host executor;
+    they and `remap_reference` agree bit for bit.  A BxHxWxC batch runs frame by frame."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    spacing = _check_spacing(spacing)
+    checked = {}
+
+    def mesher(W, H):
+        W2, H2 = _dest_size(size, W, H)
+        if (W2, H2) not in checked:
+            checked[(W2, H2)] = _check_mesh(mesh, spacing, W2, H2)
+        return checked[(W2, H2)], spacing, W2, H2
+    return _remap_frame(x, mesher, mode, border, fill)
+
+
+def warp_perspective(x, H, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0,
+                     inverse: bool = False):
+    """Perspective warp by the forward 3x3 matrix H (source -> destination, like cv2.warpPerspective without
+    WARP_INVERSE_MAP; inverse=True: H maps destination to source itself).  The map is evaluated in double at
+    the nodes of a mesh whose spacing is chosen to keep the interpolation within 2^-10 pixel; see
+    `mesh_warp`.  A destination the horizon crosses is refused."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    return _remap_frame(x, _perspective_mesher(H, size, inverse), mode, border, fill)
+
+
+def perspective_from_points(src, dst):
+    """cv2.getPerspectiveTransform: the forward 3x3 matrix (h22 = 1) that maps the four points src[k] = (x, y)
+    to dst[k]."""
+    try:
+        s = [float(v) for v in np.asarray(src, dtype=np.float64).reshape(-1)]
+        d = [float(v) for v in np.asarray(dst, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError("perspective_from_points: four points (x, y) each") from None
+    if len(s) != 8 or len(d) != 8:
+        raise ValueError("perspective_from_points: four points (x, y) each")
+    return np.asarray(_builder(C.perspective_from_points, s, d), np.float64).reshape(3, 3)
+
+
+def rectify_quad(x, quad, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0):
+    """The quadrilateral quad = (TL, TR, BR, BL), points (x, y) of the source, straightened to a rectangle
+    whose corners they become.  size=(H2, W2); default: the longer of each pair of opposite sides, rounded,
+    plus one."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    try:
+        pts = [float(v) for v in np.asarray(quad, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError("rectify_quad: four points (x, y)") from None
+    if len(pts) != 8:
+        raise ValueError("rectify_quad: four points (x, y)")
+    if size is None:
+        Hm, W2, H2 = _builder(C.quad_matrix, pts, 0, 0)
+    else:
+        W2, H2 = _dest_size(size, 1, 1)
+        Hm, W2, H2 = _builder(C.quad_matrix, pts, W2, H2)
+    return _remap_frame(x, _perspective_mesher(Hm, (H2, W2), False), mode, border, fill)
+
+
+def undistort(x, k1: float, k2: float = 0.0, f=None, center=None, mode: str = "bilinear", border: str = "constant",
+              fill: int = 0):
+    """Radial lens undistortion (cv2.undistort with K = newK = [[f, 0, cx], [0, f, cy]] and
+    dist = (k1, k2, 0, 0)); f defaults to half the diagonal, center to ((W - 1) / 2, (H - 1) / 2)."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    ff = None if f is None else float(f)
+    cc = None if center is None else [float(v) for v in center]
+
+    def mesher(W, H):
+        mesh, s = _builder(C.radial_mesh, float(k1), float(k2), ff, cc, W, H, 0)
+        return mesh, s, W, H
+    return _remap_frame(x, mesher, mode, border, fill)
+
+
+def _quantise_maps(map_x, map_y):
+    """round(4096 m) of two float maps, padded by one replicated row and column: the mesh of spacing 1."""
+    if _is_tensor(map_x) != _is_tensor(map_y):
+        raise TypeError("remap: map_x and map_y must both be tensors or both arrays")
+    if _is_tensor(map_x):
+        if map_x.shape != map_y.shape or map_x.ndim != 2 or map_x.device != map_y.device:
+            raise ValueError("remap: map_x and map_y must be two H2 x W2 maps on one device")
+        if not (map_x.is_floating_point() and map_y.is_floating_point()):
+            raise TypeError("remap: the maps must be floating point")
+        m = torch.stack([map_x, map_y], dim=2).to(torch.float64)
+        if m.numel() and not bool(torch.isfinite(m).all()):
+            raise ValueError("remap: non-finite number in the maps")
+        q = torch.round(m * 4096.0)
+        if q.numel() and float(q.abs().max()) >= _NODE_LIMIT:
+            raise ValueError("remap: a node lies at or beyond 2^18 pixels")
+        q = q.to(torch.int32)
+        q = torch.cat([q, q[-1:]], dim=0)
+        return torch.cat([q, q[:, -1:]], dim=1).contiguous()
+    mx, my = np.asarray(map_x), np.asarray(map_y)
+    if mx.shape != my.shape or mx.ndim != 2:
+        raise ValueError("remap: map_x and map_y must be two H2 x W2 maps")
+    if mx.dtype.kind != "f" or my.dtype.kind != "f":
+        raise TypeError("remap: the maps must be floating point")
+    m = np.stack([mx, my], axis=2).astype(np.float64)
+    if not np.isfinite(m).all():
+        raise ValueError("remap: non-finite number in the maps")
+    q = np.rint(m * 4096.0)
+    if q.size and np.abs(q).max() >= _NODE_LIMIT:
+        raise ValueError("remap: a node lies at or beyond 2^18 pixels")
+    return np.pad(q.astype(np.int32), ((0, 1), (0, 1), (0, 0)), mode="edge")
+
+
+def remap(x, map_x, map_y, mode: str = "bilinear", border: str = "constant", fill: int = 0):
+    """cv2.remap: out[y, x] = in(map_y[y, x], map_x[y, x]) for two float maps of the destination's size
+    (integer values are pixel centres).  The maps are quantised to Q12 where they live (CUDA maps on the
+    device) and run as a mesh of spacing 1, where nothing is interpolated; see `mesh_warp`."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    mesh = _quantise_maps(map_x, map_y)
+    H2, W2 = mesh.shape[0] - 1, mesh.shape[1] - 1
+    if not (1 <= W2 <= 65535 and 1 <= H2 <= 65535):
+        raise ValueError(f"remap: destination size {W2}x{H2} outside 1..65535")
+    return _remap_frame(x, lambda W, H: (mesh, 1, W2, H2), mode, border, fill)
+
+
+def remap_reference(x, mesh, spacing: int, size=None, mode: str = "bilinear", border: str = "constant",
+                    fill: int = 0):
+    """Golden CPU result of `mesh_warp`: the rule as a plain per-pixel loop."""
+    mode, border, fill = _warp_args(mode, border, fill)
+    spacing = _check_spacing(spacing)
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    W, H, _ = _shape(arr)
+    W2, H2 = _dest_size(size, W, H)
+    hm = _check_mesh(mesh.cpu() if _is_tensor(mesh) else mesh, spacing, W2, H2)
+    hm = hm.numpy() if _is_tensor(hm) else hm
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = _builder(C.golden_remap, np.ascontiguousarray(arr[:, :, 0] if keep else arr), hm, spacing, W2, H2, mode,
+                   border, fill)
+    return out[:, :, None] if keep else out
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -736,4 +995,6 @@ __all__ = [
     "resize", "resize_reference", "RESIZE_MODES",
     "orient", "orient_reference", "flip", "rot90", "transpose_image", "crop", "exif_orientation", "ORIENTATIONS",
     "warp_affine", "rotate", "warp_reference", "WARP_MODES", "WARP_BORDERS",
+    "warp_perspective", "perspective_from_points", "rectify_quad", "undistort", "remap", "mesh_warp",
+    "remap_reference", "MESH_SPACINGS",
 ]

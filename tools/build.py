@@ -51,6 +51,7 @@ CORE_SOURCES = [
     "core/resize.cpp",
     "core/orient.cpp",
     "core/warp.cpp",
+    "core/remap.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -67,6 +68,7 @@ CORE_SOURCES = [
     "hip/resize.hip",
     "hip/orient.hip",
     "hip/warp.hip",
+    "hip/remap.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
