@@ -24,6 +24,8 @@
 //                  [--perspective "h00;...;h22[:WxH]" | --quad "x0,y0;...;x3,y3[:WxH]" | --undistort "k1[;k2[;f[;cx;cy]]]"]
 //                  [--resize WxH[:mode]]
 //   stripe info  [--chain ...] [--channels C] [--format json]
+//   stripe label --input in.pgm [--chain C] [--connectivity 4|8] [--min-area A] [--max-area B]
+//                [--output mask.pgm] [--stats stats.json] [--backend host|device]
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -672,6 +674,85 @@ int cmd_convert(const Args& a) {
   return 0;
 }
 
+// stripe label: the optional chain on one device or on the host, then connected components of its 1-channel
+// result (stripe/components.h): N on stdout, the area-filtered mask to --output, the table to --stats.
+int cmd_label(const Args& a) {
+  STRIPE_CHECK(a.has("input"), "label needs --input");
+  const bool host_run = a.get("backend", device_count() > 0 ? "device" : "host") == "host";
+  STRIPE_CHECK(host_run || a.get("backend", "device") == "device" || a.get("backend") == "local",
+               "label: --backend is host or device, got '" << a.get("backend") << "'");
+  const int conn = parse_connectivity(a.get("connectivity", "8"));
+  const int64_t amin = a.has("min-area") ? std::stoll(a.get("min-area")) : 1;
+  const int64_t amax = a.has("max-area") ? std::stoll(a.get("max-area")) : kAreaNoLimit;
+  check_area_bounds(amin, amax);
+  const std::vector<int> devs = parse_int_list(a.get("devices"));
+  const int device = devs.empty() ? 0 : devs[0];
+  Image img = read_image(a.get("input"));
+  if (a.has("chain")) {
+    EngineConfig cfg;
+    cfg.W = img.W, cfg.H = img.H, cfg.C = img.C;
+    cfg.chain = a.get("chain");
+    if (a.has("border")) cfg.border = parse_border(a.get("border"));
+    cfg.backend = host_run ? BackendKind::Host : BackendKind::Device;
+    Group g = make_group(host_run ? "host" : "local", 1, devs);
+    PhaseTimes t;
+    img = run_group(cfg, g.comms, g.devices, img, 1, &t, nullptr);
+  }
+  check_components(img.W, img.H, img.C, conn);
+  const int W = img.W, H = img.H;
+  std::vector<int64_t> tab;
+  Image out(W, H, 1, NoInit{});
+  int N = 0;
+  if (host_run) {
+    std::vector<int32_t> labels((size_t)W * H);
+    N = cpu_components(img.data.data(), W, W, H, conn, labels.data(), W, cpu_threads());
+    tab = cpu_component_stats(labels.data(), W, W, H, N, cpu_threads());
+    for (size_t p = 0; p < labels.size(); ++p) {
+      const int64_t area = tab[(size_t)labels[p] * kStatCols];
+      out.data[p] = labels[p] != 0 && area >= amin && area <= amax ? img.data[p] : 0;
+    }
+  } else {
+    HIP_CHECK(hipSetDevice(device));
+    uint8_t *ds = nullptr, *dd = nullptr;
+    int32_t* dl = nullptr;
+    int64_t* dt = nullptr;
+    try {
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), img.bytes()));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), img.bytes()));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dl), img.bytes() * sizeof(int32_t)));
+      HIP_CHECK(hipMemcpy(ds, img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+      N = components_device(ds, W, W, H, conn, dl, W, nullptr);
+      tab.resize((size_t)(N + 1) * kStatCols);
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tab.size() * sizeof(int64_t)));
+      component_stats_device(dl, W, W, H, N, dt, nullptr);
+      area_filter_device(ds, W, W, H, dl, W, dt, N, amin, amax, dd, W, nullptr);
+      HIP_CHECK(hipMemcpy(tab.data(), dt, tab.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipFree(ds), (void)hipFree(dd), (void)hipFree(dl), (void)hipFree(dt);
+      throw;
+    }
+    HIP_CHECK(hipFree(ds));
+    HIP_CHECK(hipFree(dd));
+    HIP_CHECK(hipFree(dl));
+    HIP_CHECK(hipFree(dt));
+  }
+  if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
+  if (a.has("stats")) {
+    std::string js = "{\"n\":" + std::to_string(N) + ",\"connectivity\":" + std::to_string(conn) + ",\"components\":[";
+    for (int l = 1; l <= N; ++l) {
+      const int64_t* e = tab.data() + (size_t)l * kStatCols;
+      js += std::string(l > 1 ? "," : "") + "{\"label\":" + std::to_string(l) + ",\"area\":" + std::to_string(e[0]) +
+            ",\"bbox\":[" + std::to_string(e[1]) + "," + std::to_string(e[2]) + "," + std::to_string(e[3]) + "," +
+            std::to_string(e[4]) + "],\"sum_x\":" + std::to_string(e[5]) + ",\"sum_y\":" + std::to_string(e[6]) + "}";
+    }
+    js += "]}\n";
+    write_file_atomic(a.get("stats"), js);
+  }
+  std::printf("%d\n", N);
+  return 0;
+}
+
 int cmd_info(const Args& a) {
   const int n = device_count();
   if (a.get("format") == "json") {
@@ -984,7 +1065,7 @@ int cmd_bench(const Args& a) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: stripe <run|bench|cmp|gen|info> [options]\n"
+               "usage: stripe <run|bench|cmp|gen|convert|info|label> [options]\n"
                "  run   --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95]\n"
                "        [--chain C | --preset ref-gpu|ref-cpu] [--ranks N]\n"
                "        [--backend rccl|local|host] [--devices 0,1,..] [--border MODE] [--no-halo]\n"
@@ -1014,7 +1095,11 @@ void usage() {
                "        [--rotate DEG[:same|fit] | --warp \"a;b;c;d;e;f[:WxH]\"] [--warp-mode M] [--warp-border B]\n"
                "        [--perspective H | --quad Q | --undistort K]\n"
                "        [--resize WxH[:mode]] [--backend host]\n"
-               "  info  [--chain C] [--channels C] [--format json]\n");
+               "  info  [--chain C] [--channels C] [--format json]\n"
+               "  label --input in.pgm [--chain C] [--connectivity 4|8] [--min-area A] [--max-area B] [--output mask.pgm]\n"
+               "        [--stats stats.json] [--backend host|device]\n"
+               "            (connected components of the chain's 1-channel result: N on stdout, the area-filtered mask,\n"
+               "             and per component its area, bbox [x0, y0, x1, y1) and coordinate sums)\n");
 }
 
 }  // namespace
@@ -1028,6 +1113,7 @@ int main(int argc, char** argv) {
     if (a.cmd == "gen") return cmd_gen(a);
     if (a.cmd == "convert") return cmd_convert(a);
     if (a.cmd == "info") return cmd_info(a);
+    if (a.cmd == "label") return cmd_label(a);
     usage();
     return a.cmd.empty() || a.cmd == "help" || a.cmd == "--help" ? 0 : 2;
   } catch (const std::exception& e) {

@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "stripe/components.h"
 #include "stripe/orient.h"
 #include "stripe/rank_net.h"
 #include "stripe/remap.h"
@@ -907,6 +908,216 @@ Image cpu_remap(const Image& in, const RemapMesh& m, int threads) {
   check_mesh(m, (int64_t)m.gh() * m.gw() * 2, true);
   Image out(m.W2, m.H2, in.C, NoInit{});
   cpu_remap(in.data.data(), in.row_bytes(), in.W, in.H, in.C, out.data.data(), out.row_bytes(), m, threads);
+  return out;
+}
+
+// ---- connected components (stripe/components.h) ----
+namespace {
+
+// f(t) for t in [0, T) on T threads (the caller's among them); the first exception is rethrown after all joined.
+template <class F>
+void run_blocks(int T, F&& f) {
+  if (T <= 1) {
+    f(0);
+    return;
+  }
+  std::vector<std::exception_ptr> err((size_t)T);
+  auto guarded = [&f, &err](int t) {
+    try {
+      f(t);
+    } catch (...) {
+      err[(size_t)t] = std::current_exception();
+    }
+  };
+  std::vector<std::thread> th;
+  th.reserve((size_t)T - 1);
+  try {
+    for (int t = 1; t < T; ++t) th.emplace_back(guarded, t);
+  } catch (...) {
+    err[0] = std::current_exception();
+  }
+  if (!err[0]) guarded(0);
+  for (auto& t : th) t.join();
+  for (auto& e : err)
+    if (e) std::rethrow_exception(e);
+}
+
+// The forest in the label plane: slot i (raster index y * W + x, at y * lp + x) holds 0 (background) or its
+// parent's raster index + 1; a root holds its own.  Parents never have a larger index than their children.
+struct Forest {
+  int32_t* L;
+  int64_t lp;
+  int W;
+  int32_t* at(int64_t i) const {
+    const int64_t y = i / W;
+    return L + y * lp + (i - y * W);
+  }
+  int64_t find(int64_t i) const {
+    int64_t r = i;
+    for (int64_t p; (p = *at(r) - 1) != r;) r = p;
+    for (int64_t p; (p = *at(i) - 1) != r; i = p) *at(i) = (int32_t)(r + 1);  // compress
+    return r;
+  }
+  void unite(int64_t a, int64_t b) const {
+    a = find(a), b = find(b);
+    if (a == b) return;
+    *at(std::max(a, b)) = (int32_t)(std::min(a, b) + 1);
+  }
+  // links the run [xs, xe) of row y (head y * W + xs) with the runs of row y - 1 it touches
+  void link_up(const uint8_t* prev, int y, int xs, int xe, int conn) const {
+    const int a = conn == 8 ? std::max(xs - 1, 0) : xs, b = conn == 8 ? std::min(xe + 1, W) : xe;
+    for (int x = a; x < b; ++x)
+      if (prev[x] != 0 && (x == a || prev[x - 1] == 0)) unite((int64_t)y * W + xs, (int64_t)(y - 1) * W + x);
+  }
+};
+
+inline int32_t ld(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+inline void st(int32_t* p, int32_t v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+
+}  // namespace
+
+int cpu_components(const uint8_t* src, int64_t sp, int W, int H, int conn, int32_t* labels, int64_t lp, int threads) {
+  check_components(W, H, 1, conn);
+  STRIPE_CHECK(src && labels, "components: empty image");
+  STRIPE_CHECK(sp >= W && lp >= W, "components: pitch smaller than a row");
+  const Forest F{labels, lp, W};
+  const int T = std::max(1, std::min(threads, H));
+  auto y_of = [&](int t) { return (int)((int64_t)H * t / T); };
+  // 1. per block: the runs of every row, linked with the runs of the row above inside the block
+  run_blocks(T, [&](int t) {
+    for (int y = y_of(t); y < y_of(t + 1); ++y) {
+      const uint8_t* s = src + (int64_t)y * sp;
+      int32_t* l = labels + (int64_t)y * lp;
+      for (int x = 0; x < W;) {
+        if (s[x] == 0) {
+          l[x++] = 0;
+          continue;
+        }
+        const int xs = x;
+        const int32_t head = (int32_t)((int64_t)y * W + xs + 1);
+        while (x < W && s[x] != 0) l[x++] = head;
+        if (y > y_of(t)) F.link_up(s - sp, y, xs, x, conn);
+      }
+    }
+  });
+  // 2. the seams between the blocks
+  for (int t = 1; t < T; ++t) {
+    const int y = y_of(t);
+    const uint8_t* s = src + (int64_t)y * sp;
+    for (int x = 0; x < W;) {
+      if (s[x] == 0) {
+        ++x;
+        continue;
+      }
+      const int xs = x;
+      while (x < W && s[x] != 0) ++x;
+      F.link_up(s - sp, y, xs, x, conn);
+    }
+  }
+  // 3. flatten (every slot takes its root; a block reads other blocks' slots while they are rewritten: any
+  // value a slot ever holds is an ancestor, and roots do not change) and count the roots per block
+  std::vector<int64_t> base((size_t)T + 1, 0);
+  run_blocks(T, [&](int t) {
+    int64_t roots = 0;
+    for (int y = y_of(t); y < y_of(t + 1); ++y) {
+      int32_t* l = labels + (int64_t)y * lp;
+      for (int x = 0; x < W; ++x) {
+        const int32_t v = ld(l + x);
+        if (v == 0) continue;
+        const int64_t self = (int64_t)y * W + x;
+        int64_t r = v - 1;
+        if (r == self) {
+          ++roots;
+          continue;
+        }
+        for (int64_t p; (p = ld(F.at(r)) - 1) != r;) r = p;
+        st(l + x, (int32_t)(r + 1));
+      }
+    }
+    base[(size_t)t + 1] = roots;
+  });
+  for (int t = 0; t < T; ++t) base[(size_t)t + 1] += base[(size_t)t];
+  STRIPE_CHECK(base[(size_t)T] <= INT32_MAX, "components: too many components");
+  // 4. the roots take minus their number, in raster order
+  run_blocks(T, [&](int t) {
+    int32_t n = (int32_t)base[(size_t)t];
+    for (int y = y_of(t); y < y_of(t + 1); ++y) {
+      int32_t* l = labels + (int64_t)y * lp;
+      for (int x = 0; x < W; ++x)
+        if (l[x] != 0 && l[x] - 1 == (int64_t)y * W + x) l[x] = -(++n);
+    }
+  });
+  // 5. every pixel takes its root's number (a root's slot holds -n until its own block rewrites it to n)
+  run_blocks(T, [&](int t) {
+    for (int y = y_of(t); y < y_of(t + 1); ++y) {
+      int32_t* l = labels + (int64_t)y * lp;
+      for (int x = 0; x < W; ++x) {
+        const int32_t v = ld(l + x);
+        if (v == 0) continue;
+        const int32_t n = v < 0 ? v : ld(F.at(v - 1));
+        st(l + x, n < 0 ? -n : n);
+      }
+    }
+  });
+  return (int)base[(size_t)T];
+}
+
+std::vector<int64_t> cpu_component_stats(const int32_t* labels, int64_t lp, int W, int H, int N, int threads) {
+  STRIPE_CHECK(labels && W >= 1 && H >= 1 && lp >= W && N >= 0, "components: bad label plane");
+  const int T = std::max(1, std::min(threads, H));
+  const size_t n = (size_t)(N + 1) * kStatCols;
+  std::vector<std::vector<int64_t>> part((size_t)T);
+  run_blocks(T, [&](int t) {
+    std::vector<int64_t>& tb = part[(size_t)t];
+    tb.assign(n, 0);
+    for (int l = 0; l <= N; ++l) tb[(size_t)l * kStatCols + 1] = tb[(size_t)l * kStatCols + 2] = INT64_MAX;
+    for (int y = (int)((int64_t)H * t / T); y < (int)((int64_t)H * (t + 1) / T); ++y) {
+      const int32_t* r = labels + (int64_t)y * lp;
+      for (int x = 0; x < W;) {  // per run of equal labels
+        const int32_t l = r[x];
+        STRIPE_CHECK(l >= 0 && l <= N, "components: label " << l << " outside 0.." << N);
+        const int64_t xs = x;
+        while (x < W && r[x] == l) ++x;
+        const int64_t len = x - xs;
+        int64_t* e = tb.data() + (size_t)l * kStatCols;
+        e[0] += len;
+        e[1] = std::min(e[1], xs), e[2] = std::min<int64_t>(e[2], y);
+        e[3] = std::max<int64_t>(e[3], x), e[4] = std::max<int64_t>(e[4], y + 1);
+        e[5] += len * xs + len * (len - 1) / 2, e[6] += len * y;
+      }
+    }
+  });
+  std::vector<int64_t> out = std::move(part[0]);
+  for (int t = 1; t < T; ++t)
+    for (int l = 0; l <= N; ++l) {
+      int64_t* e = out.data() + (size_t)l * kStatCols;
+      const int64_t* p = part[(size_t)t].data() + (size_t)l * kStatCols;
+      e[0] += p[0], e[5] += p[5], e[6] += p[6];
+      e[1] = std::min(e[1], p[1]), e[2] = std::min(e[2], p[2]);
+      e[3] = std::max(e[3], p[3]), e[4] = std::max(e[4], p[4]);
+    }
+  for (int l = 0; l <= N; ++l) {
+    int64_t* e = out.data() + (size_t)l * kStatCols;
+    if (e[0] == 0) e[1] = e[2] = 0;
+  }
+  return out;
+}
+
+Image cpu_area_filter(const Image& img, int conn, int64_t amin, int64_t amax, int threads) {
+  check_components(img.W, img.H, img.C, conn);
+  check_area_bounds(amin, amax);
+  const int W = img.W, H = img.H;
+  std::vector<int32_t> labels((size_t)W * H);
+  const int N = cpu_components(img.data.data(), W, W, H, conn, labels.data(), W, threads);
+  const std::vector<int64_t> tb = cpu_component_stats(labels.data(), W, W, H, N, threads);
+  Image out(W, H, 1, NoInit{});
+  parallel_rows(0, H, 6 * (int64_t)W, std::max(1, threads), [&](int ya, int yb) {
+    for (int64_t p = (int64_t)ya * W; p < (int64_t)yb * W; ++p) {
+      const int32_t l = labels[(size_t)p];
+      const int64_t a = tb[(size_t)l * kStatCols];
+      out.data[(size_t)p] = l != 0 && a >= amin && a <= amax ? img.data[(size_t)p] : 0;
+    }
+  });
   return out;
 }
 

@@ -217,6 +217,53 @@ void launch_remap(const RemapLaunch& L, hipStream_t s) {
   launch_remap_kernel(L, s);
 }
 
+int launch_components(const ComponentsLaunch& L, hipStream_t s) {
+  // host-side shape checks before any kernel touches memory
+  STRIPE_CHECK(L.src && L.labels, "bad components launch: null src or labels");
+  check_components(L.W, L.H, 1, L.conn);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "components: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  STRIPE_CHECK(L.labels_pitch >= (int64_t)L.W,
+               "components: labels_pitch " << L.labels_pitch << " < the row's " << L.W << " elements");
+  STRIPE_CHECK((reinterpret_cast<uintptr_t>(L.labels) & 3) == 0, "components: the labels must be aligned to 4 bytes");
+  if (L.src_base)
+    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W <=
+                                            L.src_bytes,
+                 "components: source rows outside their buffer");
+  if (L.labels_base) {
+    const uint8_t* lb = reinterpret_cast<const uint8_t*>(L.labels);
+    STRIPE_CHECK(lb >= L.labels_base && (lb - L.labels_base) + ((int64_t)(L.H - 1) * L.labels_pitch + L.W) * 4 <=
+                                            L.labels_bytes,
+                 "components: label rows outside their buffer");
+  }
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  return launch_components_kernels(L, s);
+}
+
+void launch_component_stats(const ComponentStatsLaunch& L, hipStream_t s) {
+  STRIPE_CHECK(L.labels && L.stats, "bad component stats launch: null labels or stats");
+  check_components(L.W, L.H, 1, 8);
+  STRIPE_CHECK(L.N >= 0 && (int64_t)L.N <= (int64_t)L.W * L.H, "components: N = " << L.N << " outside 0..W * H");
+  STRIPE_CHECK(L.labels_pitch >= (int64_t)L.W,
+               "components: labels_pitch " << L.labels_pitch << " < the row's " << L.W << " elements");
+  STRIPE_CHECK((reinterpret_cast<uintptr_t>(L.labels) & 3) == 0 && (reinterpret_cast<uintptr_t>(L.stats) & 7) == 0,
+               "components: the labels must be aligned to 4 bytes, the table to 8");
+  (void)hipGetLastError();
+  launch_component_stats_kernels(L, s);
+}
+
+void launch_area_filter(const AreaFilterLaunch& L, hipStream_t s) {
+  STRIPE_CHECK(L.src && L.labels && L.stats && L.dst, "bad area filter launch: null src, labels, stats or dst");
+  check_components(L.W, L.H, 1, 8);
+  check_area_bounds(L.amin, L.amax);
+  STRIPE_CHECK(L.N >= 0 && (int64_t)L.N <= (int64_t)L.W * L.H, "components: N = " << L.N << " outside 0..W * H");
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W && L.dst_pitch >= (int64_t)L.W && L.labels_pitch >= (int64_t)L.W,
+               "components: pitch smaller than a row");
+  STRIPE_CHECK((reinterpret_cast<uintptr_t>(L.labels) & 3) == 0 && (reinterpret_cast<uintptr_t>(L.stats) & 7) == 0,
+               "components: the labels must be aligned to 4 bytes, the table to 8");
+  (void)hipGetLastError();
+  launch_area_filter_kernel(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

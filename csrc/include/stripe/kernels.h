@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "stripe/chain.h"
+#include "stripe/components.h"
 #include "stripe/image.h"
 #include "stripe/orient.h"
 #include "stripe/remap.h"
@@ -300,6 +301,77 @@ void launch_remap(const RemapLaunch& L, hipStream_t s);         // dispatch.cpp:
 void launch_remap_kernel(const RemapLaunch& L, hipStream_t s);  // remap.hip
 void remap_device(const uint8_t* src, int64_t src_pitch, int W, int H, int C, uint8_t* dst, int64_t dst_pitch,
                   const RemapMesh& mesh, int64_t mesh_count, hipStream_t s);
+
+// Connected components of a 1-channel mask (csrc/hip/components.hip k_ccl_*; the
+// rule: stripe/components.h).  Addressing as k_orient: 64-bit on pitched views,
+// the source pitch any value >= W at any alignment, no byte outside a source
+// row's W bytes read, nothing outside a label row's W ints written (the label
+// pitch counts int32 elements; the plane is aligned to 4 bytes).
+//
+// The label plane is the union-find forest while a call runs (a slot holds its
+// parent's raster index + 1; the numbers pass through the roots' own slots as
+// negatives), so a call needs no second plane: beyond the labels it uses
+// (H + 3) u32 of device memory, cached per device and H.  k_ccl_tile labels
+// kCclTile x kCclTile tiles in LDS, ccl_lds_bytes() of u32 local indices (LDS
+// atomics are 32 bits wide); k_ccl_number keeps one count per wave.
+// components_device returns N after the call's one host synchronisation, and
+// raises there if a union-find loop overran its step cap of W * H + 2.
+constexpr int kCclTile = 64;       // pixels per tile side
+constexpr int kCclStatSeg = 4096;  // pixels of a row that one wave of k_ccl_stats walks
+constexpr int ccl_lds_bytes() { return kCclTile * kCclTile * 4; }
+constexpr int ccl_number_lds_bytes() { return 4 * 4; }  // four waves' root counts
+constexpr int ccl_scan_lds_bytes() { return 256 * 4; }  // one partial sum per thread
+struct ComponentsLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;  // bytes
+  int W = 0, H = 0, conn = 8;
+  int32_t* labels = nullptr;
+  int64_t labels_pitch = 0;  // int32 elements
+  // optional: the allocations the views lie in (checked against the rows touched)
+  const uint8_t* src_base = nullptr;
+  int64_t src_bytes = 0;
+  const uint8_t* labels_base = nullptr;
+  int64_t labels_bytes = 0;
+};
+int launch_components(const ComponentsLaunch& L, hipStream_t s);          // dispatch.cpp: checks, then the kernels
+int launch_components_kernels(const ComponentsLaunch& L, hipStream_t s);  // components.hip
+int components_device(const uint8_t* src, int64_t src_pitch, int W, int H, int conn, int32_t* labels,
+                      int64_t labels_pitch, hipStream_t s);
+// The table of the labels 0 .. N into `stats`, (N + 1) x kStatCols int64 on the
+// device (k_ccl_stats: 64-bit atomics, exact and independent of their order; a
+// wave holds the background and its most frequent foreground label in registers
+// over kCclStatSeg pixels of a row and issues one set of atomics per horizontal
+// run of every other label).  Synchronises the stream and refuses a plane
+// that holds a label outside 0 .. N (such a label writes nothing).
+struct ComponentStatsLaunch {
+  const int32_t* labels = nullptr;
+  int64_t labels_pitch = 0;
+  int W = 0, H = 0, N = 0;
+  int64_t* stats = nullptr;
+};
+void launch_component_stats(const ComponentStatsLaunch& L, hipStream_t s);          // dispatch.cpp
+void launch_component_stats_kernels(const ComponentStatsLaunch& L, hipStream_t s);  // components.hip
+void component_stats_device(const int32_t* labels, int64_t labels_pitch, int W, int H, int N, int64_t* stats,
+                            hipStream_t s);
+// The area filter (k_ccl_select): dst = src where the pixel is foreground and
+// its label's area lies in amin .. amax, else 0.  Asynchronous.
+struct AreaFilterLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int W = 0, H = 0;
+  const int32_t* labels = nullptr;
+  int64_t labels_pitch = 0;
+  const int64_t* stats = nullptr;  // the device table of component_stats_device
+  int N = 0;
+  int64_t amin = 1, amax = kAreaNoLimit;
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+};
+void launch_area_filter(const AreaFilterLaunch& L, hipStream_t s);         // dispatch.cpp
+void launch_area_filter_kernel(const AreaFilterLaunch& L, hipStream_t s);  // components.hip
+void area_filter_device(const uint8_t* src, int64_t src_pitch, int W, int H, const int32_t* labels,
+                        int64_t labels_pitch, const int64_t* stats, int N, int64_t amin, int64_t amax, uint8_t* dst,
+                        int64_t dst_pitch, hipStream_t s);
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

@@ -791,6 +791,110 @@ PYBIND11_MODULE(_C, m) {
   }, "k_remap's tile constants: destination pixels per tile side, source pixels per side of the staged box, the "
      "smallest spacing whose nodes go to LDS, nodes per tile side, their bytes, and the LDS bytes of an instance");
 
+  // ---- connected components (stripe/components.h): labels, stats, area filter; entry points of their own ----
+  static const auto labels_to_numpy = [](const std::vector<int32_t>& l, int W, int H) {
+    py::array_t<int32_t> a(std::vector<py::ssize_t>{H, W});
+    std::memcpy(a.mutable_data(), l.data(), l.size() * sizeof(int32_t));
+    return a;
+  };
+  static const auto stats_to_numpy = [](const std::vector<int64_t>& t) {
+    py::array_t<int64_t> a(std::vector<py::ssize_t>{(py::ssize_t)(t.size() / kStatCols), kStatCols});
+    std::memcpy(a.mutable_data(), t.data(), t.size() * sizeof(int64_t));
+    return a;
+  };
+  m.def("parse_connectivity", &parse_connectivity, py::arg("token"));
+  m.def("golden_components", [labels = labels_to_numpy](const U8Array& a, int conn) {
+    const Image img = image_from_numpy(a);
+    std::vector<int32_t> l;
+    int n;
+    {
+      py::gil_scoped_release nogil;
+      n = golden_components(img, conn, &l);
+    }
+    return py::make_tuple(labels(l, img.W, img.H), n);
+  }, py::arg("image"), py::arg("connectivity") = 8, "(int32 labels HxW, N): the flood-fill oracle");
+  m.def("cpu_components", [labels = labels_to_numpy](const U8Array& a, int conn, int threads) {
+    const Image img = image_from_numpy(a);
+    check_components(img.W, img.H, img.C, conn);
+    std::vector<int32_t> l((size_t)img.W * img.H);
+    int n;
+    {
+      py::gil_scoped_release nogil;
+      n = cpu_components(img.data.data(), img.W, img.W, img.H, conn, l.data(), img.W,
+                         threads > 0 ? threads : cpu_threads());
+    }
+    return py::make_tuple(labels(l, img.W, img.H), n);
+  }, py::arg("image"), py::arg("connectivity") = 8, py::arg("threads") = 0,
+     "(int32 labels HxW, N) on the host executor: min(threads, H) row blocks");
+  using I32Array = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+  m.def("component_stats", [stats = stats_to_numpy](const I32Array& l, int n, int threads) {
+    STRIPE_CHECK(l.ndim() == 2 && l.shape(0) >= 1 && l.shape(1) >= 1, "components: labels must be HxW");
+    const int H = (int)l.shape(0), W = (int)l.shape(1);
+    std::vector<int64_t> t;
+    {
+      py::gil_scoped_release nogil;
+      t = threads == 1 ? component_stats(l.data(), W, W, H, n)
+                       : cpu_component_stats(l.data(), W, W, H, n, threads > 0 ? threads : cpu_threads());
+    }
+    return stats(t);
+  }, py::arg("labels"), py::arg("n"), py::arg("threads") = 1,
+     "int64 (n + 1, 7): area, x0, y0, x1, y1, sum_x, sum_y per label (threads = 1: the plain loop)");
+  m.def("golden_area_filter", [](const U8Array& a, int conn, int64_t amin, int64_t amax) {
+    const Image img = image_from_numpy(a);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_area_filter(img, conn, amin, amax);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("connectivity") = 8, py::arg("min_area") = 1, py::arg("max_area") = kAreaNoLimit);
+  m.def("cpu_area_filter", [](const U8Array& a, int conn, int64_t amin, int64_t amax, int threads) {
+    const Image img = image_from_numpy(a);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_area_filter(img, conn, amin, amax, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("connectivity") = 8, py::arg("min_area") = 1, py::arg("max_area") = kAreaNoLimit,
+     py::arg("threads") = 0);
+  m.def("components_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int conn, uintptr_t labels,
+                                int64_t labels_pitch, uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    return components_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, conn,
+                             reinterpret_cast<int32_t*>(labels), labels_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("connectivity"), py::arg("labels"),
+     py::arg("labels_pitch"), py::arg("stream") = 0,
+     "k_ccl_* on a pitched u8 device mask (any alignment) into an int32 device plane (pitch in elements); returns N "
+     "after the call's one synchronisation of the stream");
+  m.def("component_stats_device", [](uintptr_t labels, int64_t labels_pitch, int W, int H, int n, uintptr_t stats,
+                                     uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    component_stats_device(reinterpret_cast<const int32_t*>(labels), labels_pitch, W, H, n,
+                           reinterpret_cast<int64_t*>(stats), as_stream(stream));
+  }, py::arg("labels"), py::arg("labels_pitch"), py::arg("W"), py::arg("H"), py::arg("n"), py::arg("stats"),
+     py::arg("stream") = 0, "k_ccl_stats into an int64 (n + 1, 7) device table; synchronises the stream");
+  m.def("area_filter_device", [](uintptr_t src, int64_t src_pitch, int W, int H, uintptr_t labels, int64_t labels_pitch,
+                                 uintptr_t stats, int n, int64_t amin, int64_t amax, uintptr_t dst, int64_t dst_pitch,
+                                 uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    area_filter_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, reinterpret_cast<const int32_t*>(labels),
+                       labels_pitch, reinterpret_cast<const int64_t*>(stats), n, amin, amax,
+                       reinterpret_cast<uint8_t*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("labels"), py::arg("labels_pitch"),
+     py::arg("stats"), py::arg("n"), py::arg("min_area"), py::arg("max_area"), py::arg("dst"), py::arg("dst_pitch"),
+     py::arg("stream") = 0, "k_ccl_select: the area filter from device labels and their device table, queued on the stream");
+  m.def("components_tile", [] { return py::make_tuple(kCclTile, kCclTile); }, "k_ccl_tile's tile: (tw, th) pixels");
+  m.def("components_lds", [] {
+    py::dict d;
+    d["k_ccl_tile"] = ccl_lds_bytes();
+    d["k_ccl_number"] = ccl_number_lds_bytes();
+    d["k_ccl_scan"] = ccl_scan_lds_bytes();
+    return d;
+  }, "LDS bytes of the k_ccl_* kernels that use any");
+  m.attr("AREA_NO_LIMIT") = kAreaNoLimit;
+  m.attr("STAT_COLUMNS") = std::vector<std::string>{"area", "x0", "y0", "x1", "y1", "sum_x", "sum_y"};
+
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
         py::arg("image"), "int64 counts of shape (C, 256)");

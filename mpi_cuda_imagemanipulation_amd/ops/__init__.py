@@ -979,6 +979,163 @@ def remap_reference(x, mesh, spacing: int, size=None, mode: str = "bilinear", bo
     return out[:, :, None] if keep else out
 
 
+# ---- connected components (csrc/include/stripe/components.h): labels, stats, area filter ----
+STAT_COLUMNS = tuple(C.STAT_COLUMNS)
+
+
+def _mask_shape(x):
+    """(W, H) of a mask HxW or HxWx1; an RGB frame and every other shape is refused."""
+    if x.ndim == 4:
+        raise ValueError(f"components: one frame at a time, got a batch of shape {tuple(x.shape)}")
+    if x.ndim == 3 and x.shape[2] == 3:
+        raise ValueError("components: needs a 1-channel image, got C = 3; convert first (gray, threshold, ...)")
+    if x.ndim == 2 or (x.ndim == 3 and x.shape[2] == 1):
+        return int(x.shape[1]), int(x.shape[0])
+    raise ValueError(f"components: the mask must be HxW or HxWx1 uint8, got shape {tuple(x.shape)}")
+
+
+def _connectivity(connectivity):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f"components: connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _area_bounds(min_area, max_area):
+    for name, v in (("min_area", min_area), ("max_area", max_area)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise ValueError(f"components: {name} must be an integer, got {v!r}")
+    amin = int(min_area)
+    amax = C.AREA_NO_LIMIT if max_area is None else int(max_area)
+    if amin < 1:
+        raise ValueError(f"components: min_area must be at least 1, got {amin}")
+    if amax < amin:
+        raise ValueError(f"components: max_area {amax} < min_area {amin}")
+    return amin, amax
+
+
+def _device_mask(x, W):
+    """A CUDA mask as the pitched HxW view the kernels take (only a row's pixels must be packed)."""
+    if x.dtype != torch.uint8:
+        raise TypeError("image tensor must be uint8")
+    x2 = x[:, :, 0] if x.ndim == 3 else x
+    packed = (x2.stride(1) == 1 or W == 1) and (x2.stride(0) >= W or x2.shape[0] == 1)
+    return x2 if packed else x2.contiguous()
+
+
+def _host_mask(x):
+    arr = x.numpy() if _is_tensor(x) else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    return np.ascontiguousarray(arr[:, :, 0] if arr.ndim == 3 else arr)
+
+
+def _device_label(xc, W, H, conn):
+    labels = torch.empty((H, W), dtype=torch.int32, device=xc.device)
+    with torch.cuda.device(xc.device):
+        stream = torch.cuda.current_stream(xc.device)
+        n = _builder(C.components_device, xc.data_ptr(), xc.stride(0) if H > 1 else W, W, H, conn, labels.data_ptr(), W,
+                     stream.cuda_stream)
+    # keep the input alive until the stream has consumed it
+    xc.record_stream(stream)
+    return labels, n
+
+
+def _device_stats(labels, n):
+    H, W = labels.shape
+    lc = labels if labels.stride(1) == 1 and labels.stride(0) >= W else labels.contiguous()
+    table = torch.empty((n + 1, len(STAT_COLUMNS)), dtype=torch.int64, device=labels.device)
+    with torch.cuda.device(labels.device):
+        stream = torch.cuda.current_stream(labels.device)
+        _builder(C.component_stats_device, lc.data_ptr(), lc.stride(0), W, H, n, table.data_ptr(), stream.cuda_stream)
+    lc.record_stream(stream)
+    return lc, table
+
+
+def label(x, connectivity: int = 8):
+    """Connected components of a mask: (labels, n).
+
+    x: HxW or HxWx1 uint8; a pixel is foreground iff it is != 0.  connectivity 4 (W/E/N/S) or 8 (with the
+    diagonals).  labels: int32 HxW, 0 the background, the components numbered 1..n in raster order of their
+    first pixel (scipy.ndimage.label's numbering).  A CUDA tensor runs on the k_ccl_* HIP kernels on torch's
+    current stream and gives a CUDA tensor (the call synchronises the stream once, to read n); numpy arrays /
+    CPU tensors run on the threaded host executor and keep their container.  Bit-identical to
+    `label_reference`."""
+    W, H = _mask_shape(x)
+    conn = _connectivity(connectivity)
+    if _is_tensor(x) and x.is_cuda:
+        return _device_label(_device_mask(x, W), W, H, conn)
+    labels, n = _builder(C.cpu_components, _host_mask(x), conn)
+    return (torch.from_numpy(labels) if _is_tensor(x) else labels), n
+
+
+def label_reference(x, connectivity: int = 8):
+    """Golden CPU result of `label`: a raster scan that flood-fills every unlabelled foreground pixel."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _mask_shape(arr)
+    return _builder(C.golden_components, _host_mask(arr), _connectivity(connectivity))
+
+
+def component_stats(labels, n: int):
+    """int64 numpy table (n + 1, 7) of the labels 0..n: area, x0, y0, x1, y1, sum_x, sum_y (STAT_COLUMNS).
+
+    Row 0 is the background; x0, y0 inclusive, x1, y1 exclusive; sum_x / area is the centroid.  CUDA labels run
+    on k_ccl_stats."""
+    if labels.ndim != 2:
+        raise ValueError(f"components: labels must be HxW, got shape {tuple(labels.shape)}")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"components: n must not be negative, got {n}")
+    if _is_tensor(labels) and labels.is_cuda:
+        if labels.dtype != torch.int32:
+            raise TypeError("labels must be int32")
+        return _device_stats(labels, n)[1].cpu().numpy()
+    arr = labels.numpy() if _is_tensor(labels) else np.asarray(labels)
+    if arr.dtype != np.int32:
+        raise TypeError("labels must be int32")
+    return _builder(C.component_stats, np.ascontiguousarray(arr), n, 0)
+
+
+def area_filter(x, min_area: int = 1, max_area=None, connectivity: int = 8):
+    """Keep the components whose area lies in min_area..max_area (None: no limit); everything else becomes 0.
+
+    The result has the shape, dtype and container of x (kept pixels keep their byte), so it can go back into a
+    chain."""
+    W, H = _mask_shape(x)
+    conn = _connectivity(connectivity)
+    amin, amax = _area_bounds(min_area, max_area)
+    if _is_tensor(x) and x.is_cuda:
+        xc = _device_mask(x, W)
+        labels, n = _device_label(xc, W, H, conn)
+        labels, table = _device_stats(labels, n)
+        out = torch.empty((H, W), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            _builder(C.area_filter_device, xc.data_ptr(), xc.stride(0) if H > 1 else W, W, H, labels.data_ptr(), W,
+                     table.data_ptr(), n, amin, amax, out.data_ptr(), W, stream.cuda_stream)
+        # keep the input and the temporaries alive until the stream has consumed them
+        for t in (xc, labels, table):
+            t.record_stream(stream)
+        return out[:, :, None] if x.ndim == 3 else out
+    out = _builder(C.cpu_area_filter, _host_mask(x), conn, amin, amax)
+    if x.ndim == 3:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if _is_tensor(x) else out
+
+
+def remove_small_objects(x, min_area: int, connectivity: int = 8):
+    """Drop every component of fewer than min_area pixels."""
+    return area_filter(x, min_area, None, connectivity)
+
+
+def keep_largest(x, connectivity: int = 8):
+    """Keep the components of the largest area (all of them on a tie); a frame without foreground stays empty."""
+    labels, n = label(x, connectivity)
+    if n == 0:
+        return area_filter(x, 1, None, connectivity)
+    top = int(component_stats(labels, n)[1:, 0].max())
+    return area_filter(x, top, None, connectivity)
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
@@ -997,4 +1154,6 @@ __all__ = [
     "warp_affine", "rotate", "warp_reference", "WARP_MODES", "WARP_BORDERS",
     "warp_perspective", "perspective_from_points", "rectify_quad", "undistort", "remap", "mesh_warp",
     "remap_reference", "MESH_SPACINGS",
+    "label", "label_reference", "component_stats", "area_filter", "remove_small_objects", "keep_largest",
+    "STAT_COLUMNS",
 ]

@@ -52,6 +52,7 @@ CORE_SOURCES = [
     "core/orient.cpp",
     "core/warp.cpp",
     "core/remap.cpp",
+    "core/components.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -69,6 +70,7 @@ CORE_SOURCES = [
     "hip/orient.hip",
     "hip/warp.hip",
     "hip/remap.hip",
+    "hip/components.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
