@@ -26,6 +26,8 @@
 //   stripe info  [--chain ...] [--channels C] [--format json]
 //   stripe label --input in.pgm [--chain C] [--connectivity 4|8] [--min-area A] [--max-area B]
 //                [--output mask.pgm] [--stats stats.json] [--backend host|device]
+//   stripe distance --input in.pgm [--chain C] [--to background|foreground] [--backend host|device] --output d.pgm
+//                   [--erode R | --dilate R | --open R | --close R]
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -753,6 +755,89 @@ int cmd_label(const Args& a) {
   return 0;
 }
 
+// stripe distance: the optional chain on one device or on the host, then the distance transform of its 1-channel
+// result (stripe/distance.h): the u8 form to --output, or with --erode / --dilate / --open / --close R the mask of that
+// disc operation; the largest finite d^2 (or "none") on stdout.
+int cmd_distance(const Args& a) {
+  STRIPE_CHECK(a.has("input"), "distance needs --input");
+  const bool host_run = a.get("backend", device_count() > 0 ? "device" : "host") == "host";
+  STRIPE_CHECK(host_run || a.get("backend", "device") == "device" || a.get("backend") == "local",
+               "distance: --backend is host or device, got '" << a.get("backend") << "'");
+  const bool to_fg = parse_distance_to(a.get("to", "background"));
+  int nops = 0;
+  DiskOp op = DiskOp::Erode;
+  double radius = 0.0;
+  for (const char* name : {"erode", "dilate", "open", "close"})
+    if (a.has(name)) {
+      ++nops, op = parse_disk_op(name);
+      try {
+        size_t used = 0;
+        radius = std::stod(a.get(name), &used);
+        STRIPE_CHECK(used == a.get(name).size(), "trailing characters");
+      } catch (const std::exception&) {
+        fail("distance: --" + std::string(name) + " needs a radius, got '" + a.get(name) + "'");
+      }
+    }
+  STRIPE_CHECK(nops <= 1, "distance: at most one of --erode, --dilate, --open, --close");
+  const int32_t t = check_radius(radius);
+  const std::vector<int> devs = parse_int_list(a.get("devices"));
+  const int device = devs.empty() ? 0 : devs[0];
+  Image img = read_image(a.get("input"));
+  if (a.has("chain")) {
+    EngineConfig cfg;
+    cfg.W = img.W, cfg.H = img.H, cfg.C = img.C;
+    cfg.chain = a.get("chain");
+    if (a.has("border")) cfg.border = parse_border(a.get("border"));
+    cfg.backend = host_run ? BackendKind::Host : BackendKind::Device;
+    Group g = make_group(host_run ? "host" : "local", 1, devs);
+    PhaseTimes pt;
+    img = run_group(cfg, g.comms, g.devices, img, 1, &pt, nullptr);
+  }
+  check_distance(img.W, img.H, img.C);
+  const int W = img.W, H = img.H;
+  std::vector<int32_t> d2((size_t)W * H);
+  Image out(W, H, 1, NoInit{});
+  if (host_run) {
+    cpu_distance(img.data.data(), W, W, H, to_fg, d2.data(), W, cpu_threads());
+    if (nops)
+      out = cpu_disk_morph(img, op, radius, cpu_threads());
+    else
+      for (size_t p = 0; p < d2.size(); ++p) out.data[p] = distance_u8(d2[p]);
+  } else {
+    HIP_CHECK(hipSetDevice(device));
+    uint8_t *ds = nullptr, *dd = nullptr;
+    int32_t* dq = nullptr;
+    try {
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), img.bytes()));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), img.bytes()));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dq), img.bytes() * sizeof(int32_t)));
+      HIP_CHECK(hipMemcpy(ds, img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+      distance_device(ds, W, W, H, to_fg, (int)DistanceMode::Squared, 0, dq, W, nullptr);
+      if (nops)
+        disk_morph_device(ds, W, W, H, (int)op, t, dd, W, nullptr);
+      else
+        distance_device(ds, W, W, H, to_fg, (int)DistanceMode::U8, 0, dd, W, nullptr);
+      HIP_CHECK(hipMemcpy(d2.data(), dq, d2.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipFree(ds), (void)hipFree(dd), (void)hipFree(dq);
+      throw;
+    }
+    HIP_CHECK(hipFree(ds));
+    HIP_CHECK(hipFree(dd));
+    HIP_CHECK(hipFree(dq));
+  }
+  if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
+  int32_t top = -1;
+  for (int32_t v : d2)
+    if (v != kDistanceNone) top = std::max(top, v);
+  if (top < 0)
+    std::printf("none\n");
+  else
+    std::printf("%d\n", top);
+  return 0;
+}
+
 int cmd_info(const Args& a) {
   const int n = device_count();
   if (a.get("format") == "json") {
@@ -1065,7 +1150,7 @@ int cmd_bench(const Args& a) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: stripe <run|bench|cmp|gen|convert|info|label> [options]\n"
+               "usage: stripe <run|bench|cmp|gen|convert|info|label|distance> [options]\n"
                "  run   --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95]\n"
                "        [--chain C | --preset ref-gpu|ref-cpu] [--ranks N]\n"
                "        [--backend rccl|local|host] [--devices 0,1,..] [--border MODE] [--no-halo]\n"
@@ -1099,7 +1184,11 @@ void usage() {
                "  label --input in.pgm [--chain C] [--connectivity 4|8] [--min-area A] [--max-area B] [--output mask.pgm]\n"
                "        [--stats stats.json] [--backend host|device]\n"
                "            (connected components of the chain's 1-channel result: N on stdout, the area-filtered mask,\n"
-               "             and per component its area, bbox [x0, y0, x1, y1) and coordinate sums)\n");
+               "             and per component its area, bbox [x0, y0, x1, y1) and coordinate sums)\n"
+               "  distance --input in.pgm [--chain C] [--to background|foreground] [--backend host|device] --output d.pgm\n"
+               "        [--erode R | --dilate R | --open R | --close R]\n"
+               "            (exact Euclidean distance transform of the chain's 1-channel result: min(255, floor(d)) as a PGM,\n"
+               "             or the mask of the disc operation of radius R; the largest finite d^2 or 'none' on stdout)\n");
 }
 
 }  // namespace
@@ -1114,6 +1203,7 @@ int main(int argc, char** argv) {
     if (a.cmd == "convert") return cmd_convert(a);
     if (a.cmd == "info") return cmd_info(a);
     if (a.cmd == "label") return cmd_label(a);
+    if (a.cmd == "distance") return cmd_distance(a);
     usage();
     return a.cmd.empty() || a.cmd == "help" || a.cmd == "--help" ? 0 : 2;
   } catch (const std::exception& e) {

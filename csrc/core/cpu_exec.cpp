@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "stripe/components.h"
+#include "stripe/distance.h"
 #include "stripe/orient.h"
 #include "stripe/rank_net.h"
 #include "stripe/remap.h"
@@ -1119,6 +1120,119 @@ Image cpu_area_filter(const Image& img, int conn, int64_t amin, int64_t amax, in
     }
   });
   return out;
+}
+
+// ---- distance transform (stripe/distance.h) ----
+namespace {
+
+constexpr int32_t kNoG = -1;  // g: the column has no site
+
+// One row of the squared distance from its g values: the lower envelope of the parabolas
+// (x - i)^2 + g(i)^2 over the columns i that have a site (Meijster's scan, integers only).
+// s: the envelope's columns, t: where each takes over; both W entries.
+void edt_row(const int32_t* g, int W, int32_t* out, int32_t* s, int32_t* t) {
+  const auto F = [g](int64_t x, int64_t i) { return (x - i) * (x - i) + (int64_t)g[i] * g[i]; };
+  int q = -1;
+  for (int u = 0; u < W; ++u) {
+    if (g[u] == kNoG) continue;
+    while (q >= 0 && F(t[q], s[q]) > F(t[q], u)) --q;
+    if (q < 0) {
+      q = 0, s[0] = u, t[0] = 0;
+    } else {
+      // the first x at which u is no worse than s[q]: 1 + floor(num / den), num >= 0 after the loop above
+      const int64_t i = s[q];
+      const int64_t num = (int64_t)u * u - i * i + (int64_t)g[u] * g[u] - (int64_t)g[i] * g[i], den = 2 * (u - i);
+      const int64_t w = 1 + (num >= 0 ? num / den : -((-num + den - 1) / den));
+      if (w < W) ++q, s[q] = u, t[q] = (int32_t)std::max<int64_t>(w, 0);
+    }
+  }
+  if (q < 0) {
+    std::fill(out, out + W, kDistanceNone);
+    return;
+  }
+  for (int u = W - 1; u >= 0; --u) {
+    out[u] = (int32_t)F(u, s[q]);
+    if (u == t[q] && q > 0) --q;
+  }
+}
+
+}  // namespace
+
+void cpu_distance(const uint8_t* src, int64_t sp, int W, int H, bool to_foreground, int32_t* out, int64_t op,
+                  int threads) {
+  check_distance(W, H, 1);
+  STRIPE_CHECK(src && out, "distance: empty image");
+  STRIPE_CHECK(sp >= W && op >= W, "distance: pitch smaller than a row");
+  const int T = std::max(1, threads);
+  // column pass: g into the output plane, column blocks of whole cache lines, rows walked down and up
+  constexpr int kColBlock = 256;
+  const int ncb = (int)div_up(W, kColBlock);
+  const int TC = std::min(T, ncb);
+  run_blocks(TC, [&](int tb) {
+    for (int cb = (int)((int64_t)ncb * tb / TC); cb < (int)((int64_t)ncb * (tb + 1) / TC); ++cb) {
+      const int xa = cb * kColBlock, xb = std::min(W, xa + kColBlock);
+      for (int y = 0; y < H; ++y) {
+        const uint8_t* r = src + (int64_t)y * sp;
+        int32_t* o = out + (int64_t)y * op;
+        const int32_t* up = y > 0 ? o - op : nullptr;
+        for (int x = xa; x < xb; ++x)
+          o[x] = (r[x] != 0) == to_foreground ? 0 : (up && up[x] != kNoG ? up[x] + 1 : kNoG);
+      }
+      for (int y = H - 2; y >= 0; --y) {
+        int32_t* o = out + (int64_t)y * op;
+        const int32_t* dn = o + op;
+        for (int x = xa; x < xb; ++x)
+          if (dn[x] != kNoG && (o[x] == kNoG || dn[x] + 1 < o[x])) o[x] = dn[x] + 1;
+      }
+    }
+  });
+  // row pass, in place through a copy of the row's g
+  parallel_rows(0, H, 16 * (int64_t)W, T, [&](int ya, int yb) {
+    std::vector<int32_t> g((size_t)W), s((size_t)W), t((size_t)W);
+    for (int y = ya; y < yb; ++y) {
+      int32_t* o = out + (int64_t)y * op;
+      std::copy(o, o + W, g.begin());
+      edt_row(g.data(), W, o, s.data(), t.data());
+    }
+  });
+}
+
+namespace {
+
+template <class F>
+Image distance_map(const Image& img, bool to_foreground, int threads, F&& f) {
+  check_distance(img.W, img.H, img.C);
+  const int W = img.W, H = img.H;
+  std::vector<int32_t> d((size_t)W * H);
+  cpu_distance(img.data.data(), W, W, H, to_foreground, d.data(), W, threads);
+  Image out(W, H, 1, NoInit{});
+  parallel_rows(0, H, 5 * (int64_t)W, std::max(1, threads), [&](int ya, int yb) {
+    for (int64_t p = (int64_t)ya * W; p < (int64_t)yb * W; ++p) out.data[(size_t)p] = f(d[(size_t)p]);
+  });
+  return out;
+}
+
+}  // namespace
+
+Image cpu_distance_u8(const Image& img, bool to_foreground, int threads) {
+  return distance_map(img, to_foreground, threads, [](int32_t d2) { return distance_u8(d2); });
+}
+
+Image cpu_distance_mask(const Image& img, bool to_foreground, int32_t t, bool keep_above, int threads) {
+  check_distance_mode((int)DistanceMode::MaskAbove, t);
+  return distance_map(img, to_foreground, threads, [=](int32_t d2) { return distance_mask(d2, t, keep_above); });
+}
+
+Image cpu_disk_morph(const Image& img, DiskOp op, double radius, int threads) {
+  check_distance(img.W, img.H, img.C);
+  const int32_t t = check_radius(radius);
+  switch (op) {
+    case DiskOp::Erode: return cpu_distance_mask(img, false, t, true, threads);
+    case DiskOp::Dilate: return cpu_distance_mask(img, true, t, false, threads);
+    case DiskOp::Open: return cpu_distance_mask(cpu_distance_mask(img, false, t, true, threads), true, t, false, threads);
+    case DiskOp::Close: return cpu_distance_mask(cpu_distance_mask(img, true, t, false, threads), false, t, true, threads);
+  }
+  fail("distance: unknown disc operation");
 }
 
 }  // namespace stripe

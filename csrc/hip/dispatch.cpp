@@ -264,6 +264,34 @@ void launch_area_filter(const AreaFilterLaunch& L, hipStream_t s) {
   launch_area_filter_kernel(L, s);
 }
 
+namespace {
+void check_distance_launch(const DistanceLaunch& L) {
+  // host-side shape checks before any kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad distance launch: null src or dst");
+  check_distance(L.W, L.H, 1);
+  check_distance_mode(L.mode, L.t);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "distance: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W,
+               "distance: dst_pitch " << L.dst_pitch << " < the row's " << L.W << " elements");
+  STRIPE_CHECK(L.mode != (int)DistanceMode::Squared || (reinterpret_cast<uintptr_t>(L.dst) & 3) == 0,
+               "distance: the int32 plane must be aligned to 4 bytes");
+}
+}  // namespace
+
+void launch_distance(const DistanceLaunch& L, hipStream_t s) {
+  check_distance_launch(L);
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_distance_kernels(L, s);
+}
+
+void launch_disk_morph(const DistanceLaunch& L, int op, hipStream_t s) {
+  STRIPE_CHECK(op >= 0 && op <= (int)DiskOp::Close, "distance: unknown disc operation " << op);
+  check_distance_launch(L);
+  STRIPE_CHECK(L.mode != (int)DistanceMode::Squared, "distance: a disc operation stores a u8 mask");
+  (void)hipGetLastError();
+  launch_disk_morph_kernels(L, op, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

@@ -11,6 +11,7 @@
 
 #include "stripe/chain.h"
 #include "stripe/components.h"
+#include "stripe/distance.h"
 #include "stripe/image.h"
 #include "stripe/orient.h"
 #include "stripe/remap.h"
@@ -372,6 +373,54 @@ void launch_area_filter_kernel(const AreaFilterLaunch& L, hipStream_t s);  // co
 void area_filter_device(const uint8_t* src, int64_t src_pitch, int W, int H, const int32_t* labels,
                         int64_t labels_pitch, const int64_t* stats, int N, int64_t amin, int64_t amax, uint8_t* dst,
                         int64_t dst_pitch, hipStream_t s);
+
+// Exact squared Euclidean distance transform of a 1-channel mask and the disc
+// morphology on it (csrc/hip/distance.hip k_edt_*; the rule: stripe/distance.h).
+// Addressing as k_orient: 64-bit on pitched views, the source pitch any value
+// >= W at any alignment, no byte outside a source row's W bytes read, nothing
+// outside a destination row's W elements written (the pitch of an int32 plane
+// counts elements; the plane is aligned to 4 bytes).
+//
+// Column pass: k_edt_bits packs the site bits of bands of kEdtBand rows into one
+// u64 per column and band, k_edt_carry walks the H / kEdtBand words per column,
+// k_edt_band writes g (u16, 0xFFFF: no site in the column).  Row pass: k_edt_row,
+// one workgroup of kEdtRowThreads per row (kEdtRowsPerGroup = 1) with g and the
+// arg-mins in LDS, edt_row_lds_bytes(wmax) for the width class wmax of
+// kEdtWidths; divide and conquer on the monotone arg-min, O(W log W) per row
+// whatever the mask holds; ranges of more than kEdtLong candidates are scanned
+// by a wave each from a list of kEdtList entries.  The store is templated on
+// int32 d2 / u8 floor(sqrt) / u8 mask.  No host synchronisation; scratch
+// (2 B / pixel of g and 1 bit / pixel of site words, for open / close one u8
+// mask) is cached per device, stream, W and H until distance_release_scratch.
+constexpr int kEdtBand = 64;          // rows per band of the column pass: one u64 of site bits
+constexpr int kEdtRowThreads = 512;   // threads of a row-pass workgroup
+constexpr int kEdtRowsPerGroup = 1;   // rows per row-pass workgroup
+constexpr int kEdtLong = 64;          // a range of more candidates than this is scanned by a wave
+constexpr int kEdtList = 1024;        // entries of a level's list of long ranges
+constexpr int kEdtCounters = 20;      // one list length per level (at most 17)
+constexpr int kEdtWidths[3] = {4096, 16384, 32768};  // the row pass's LDS classes: W <= these
+constexpr int edt_width_class(int W) { return W <= kEdtWidths[0] ? 0 : W <= kEdtWidths[1] ? 1 : 2; }
+constexpr int edt_row_lds_bytes(int wmax) { return 4 * wmax + 2 * kEdtList + 4 * kEdtCounters; }
+struct DistanceLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;  // bytes
+  int W = 0, H = 0;
+  bool to_foreground = false;
+  int mode = 0;   // DistanceMode
+  int64_t t = 0;  // the masks' threshold
+  void* dst = nullptr;    // int32 (Squared) or u8
+  int64_t dst_pitch = 0;  // elements of the destination's type
+};
+void launch_distance(const DistanceLaunch& L, hipStream_t s);          // dispatch.cpp: checks, then the kernels
+void launch_distance_kernels(const DistanceLaunch& L, hipStream_t s);  // distance.hip
+// op: DiskOp; L.t = floor(r^2); L.mode and L.to_foreground are set per step.
+void launch_disk_morph(const DistanceLaunch& L, int op, hipStream_t s);          // dispatch.cpp
+void launch_disk_morph_kernels(const DistanceLaunch& L, int op, hipStream_t s);  // distance.hip
+void distance_device(const uint8_t* src, int64_t src_pitch, int W, int H, bool to_foreground, int mode, int64_t t,
+                     void* dst, int64_t dst_pitch, hipStream_t s);
+void disk_morph_device(const uint8_t* src, int64_t src_pitch, int W, int H, int op, int64_t t, uint8_t* dst,
+                       int64_t dst_pitch, hipStream_t s);
+void distance_release_scratch();  // frees the cached scratch of every device (waits for the devices)
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

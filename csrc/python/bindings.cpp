@@ -895,6 +895,129 @@ PYBIND11_MODULE(_C, m) {
   m.attr("AREA_NO_LIMIT") = kAreaNoLimit;
   m.attr("STAT_COLUMNS") = std::vector<std::string>{"area", "x0", "y0", "x1", "y1", "sum_x", "sum_y"};
 
+  // ---- distance transform and disc morphology (stripe/distance.h); entry points of their own ----
+  static const auto plane_to_numpy = [](const std::vector<int32_t>& d, int W, int H) {
+    py::array_t<int32_t> a(std::vector<py::ssize_t>{H, W});
+    std::memcpy(a.mutable_data(), d.data(), d.size() * sizeof(int32_t));
+    return a;
+  };
+  m.def("golden_distance", [plane = plane_to_numpy](const U8Array& a, bool to_foreground) {
+    const Image img = image_from_numpy(a);
+    std::vector<int32_t> d;
+    {
+      py::gil_scoped_release nogil;
+      golden_distance(img, to_foreground, &d);
+    }
+    return plane(d, img.W, img.H);
+  }, py::arg("image"), py::arg("to_foreground") = false,
+     "int32 squared distances HxW: the column scans and the brute-force minimum over every column, O(W^2 H)");
+  m.def("cpu_distance", [plane = plane_to_numpy](const U8Array& a, bool to_foreground, int threads) {
+    const Image img = image_from_numpy(a);
+    check_distance(img.W, img.H, img.C);
+    std::vector<int32_t> d((size_t)img.W * img.H);
+    {
+      py::gil_scoped_release nogil;
+      cpu_distance(img.data.data(), img.W, img.W, img.H, to_foreground, d.data(), img.W,
+                   threads > 0 ? threads : cpu_threads());
+    }
+    return plane(d, img.W, img.H);
+  }, py::arg("image"), py::arg("to_foreground") = false, py::arg("threads") = 0,
+     "int32 squared distances HxW on the host executor (column blocks, then lower envelopes over row blocks)");
+  m.def("golden_distance_u8", [](const U8Array& a, bool to_foreground) {
+    const Image img = image_from_numpy(a);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_distance_u8(img, to_foreground);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("to_foreground") = false);
+  m.def("golden_distance_mask", [](const U8Array& a, bool to_foreground, int64_t t, bool keep_above) {
+    const Image img = image_from_numpy(a);
+    check_distance_mode((int)DistanceMode::MaskAbove, t);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_distance_mask(img, to_foreground, (int32_t)t, keep_above);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("to_foreground"), py::arg("t"), py::arg("keep_above"));
+  m.def("cpu_distance_u8", [](const U8Array& a, bool to_foreground, int threads) {
+    const Image img = image_from_numpy(a);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_distance_u8(img, to_foreground, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("to_foreground") = false, py::arg("threads") = 0);
+  m.def("cpu_distance_mask", [](const U8Array& a, bool to_foreground, int64_t t, bool keep_above, int threads) {
+    const Image img = image_from_numpy(a);
+    check_distance_mode((int)DistanceMode::MaskAbove, t);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_distance_mask(img, to_foreground, (int32_t)t, keep_above, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("to_foreground"), py::arg("t"), py::arg("keep_above"), py::arg("threads") = 0);
+  m.def("golden_disk_morph", [](const U8Array& a, const std::string& op, double radius) {
+    const Image img = image_from_numpy(a);
+    const DiskOp o = parse_disk_op(op);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_disk_morph(img, o, radius);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("radius"), "erode / dilate / open / close by the disc {dx^2 + dy^2 <= floor(r^2)}");
+  m.def("cpu_disk_morph", [](const U8Array& a, const std::string& op, double radius, int threads) {
+    const Image img = image_from_numpy(a);
+    const DiskOp o = parse_disk_op(op);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = cpu_disk_morph(img, o, radius, threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("radius"), py::arg("threads") = 0);
+  m.def("check_radius", [](double r) { return (int64_t)check_radius(r); }, py::arg("radius"),
+        "floor(r^2), the threshold of a disc of radius r; refuses a negative or non-finite radius");
+  m.def("distance_device", [](uintptr_t src, int64_t src_pitch, int W, int H, bool to_foreground, int mode, int64_t t,
+                              uintptr_t dst, int64_t dst_pitch, uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    distance_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, to_foreground, mode, t,
+                    reinterpret_cast<void*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("to_foreground"), py::arg("mode"),
+     py::arg("t"), py::arg("dst"), py::arg("dst_pitch"), py::arg("stream") = 0,
+     "k_edt_* on a pitched u8 device mask (any alignment); mode 0: int32 d^2 (pitch in elements), 1: u8 floor(sqrt), "
+     "2 / 3: u8 mask d^2 > t / d^2 <= t; queued on the stream, no synchronisation");
+  m.def("disk_morph_device", [](uintptr_t src, int64_t src_pitch, int W, int H, const std::string& op, int64_t t,
+                                uintptr_t dst, int64_t dst_pitch, uintptr_t stream) {
+    const int o = (int)parse_disk_op(op);
+    py::gil_scoped_release nogil;
+    disk_morph_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, o, t, reinterpret_cast<uint8_t*>(dst),
+                      dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("op"), py::arg("t"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("stream") = 0,
+     "erode / dilate (one column and one row pass) or open / close (two, through a cached u8 mask) with t = floor(r^2)");
+  m.def("distance_release_scratch", [] {
+    py::gil_scoped_release nogil;
+    distance_release_scratch();
+  }, "free the cached device scratch of the distance transform");
+  m.def("distance_tile", [] { return py::make_tuple(kEdtBand, kEdtRowThreads, kEdtRowsPerGroup); },
+        "(rows per band of the column pass, threads of a row-pass workgroup, rows per row-pass workgroup)");
+  m.def("distance_widths", [] { return std::vector<int>(kEdtWidths, kEdtWidths + 3); },
+        "the row pass's LDS classes: the largest W of each");
+  m.def("distance_lds", [] {
+    py::dict d;
+    for (int w : kEdtWidths) d[py::int_(w)] = edt_row_lds_bytes(w);
+    return d;
+  }, "LDS bytes of k_edt_row per width class (the other k_edt_* kernels use none)");
+  m.attr("DISTANCE_NONE") = (int64_t)kDistanceNone;
+  m.attr("DISTANCE_MAX_SIDE") = kDistanceMaxSide;
+  m.attr("DISTANCE_MODES") = std::vector<std::string>{"squared", "u8", "mask_above", "mask_within"};
+
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
         py::arg("image"), "int64 counts of shape (C, 256)");

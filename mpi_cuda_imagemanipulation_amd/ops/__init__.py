@@ -1136,9 +1136,150 @@ def keep_largest(x, connectivity: int = 8):
     return area_filter(x, top, None, connectivity)
 
 
+# ---- distance transform and disc morphology (csrc/include/stripe/distance.h) ----
+DISTANCE_NONE = int(C.DISTANCE_NONE)
+DISTANCE_OUTPUTS = ("squared", "float", "u8")
+_DISTANCE_MODE = {name: k for k, name in enumerate(C.DISTANCE_MODES)}
+
+
+def _distance_shape(x):
+    """(W, H) of a mask HxW or HxWx1 within the side limit; everything else is refused."""
+    if x.ndim == 4:
+        raise ValueError(f"distance: one frame at a time, got a batch of shape {tuple(x.shape)}")
+    if x.ndim == 3 and x.shape[2] == 3:
+        raise ValueError("distance: needs a 1-channel image, got C = 3; convert first (gray, threshold, ...)")
+    if not (x.ndim == 2 or (x.ndim == 3 and x.shape[2] == 1)):
+        raise ValueError(f"distance: the mask must be HxW or HxWx1 uint8, got shape {tuple(x.shape)}")
+    W, H = int(x.shape[1]), int(x.shape[0])
+    if W < 1 or H < 1:
+        raise ValueError(f"distance: empty image ({W}x{H})")
+    if W > C.DISTANCE_MAX_SIDE or H > C.DISTANCE_MAX_SIDE:
+        raise ValueError(f"distance: {W}x{H} has a side above {C.DISTANCE_MAX_SIDE}")
+    return W, H
+
+
+def _distance_to(to):
+    if to not in ("background", "foreground"):
+        raise ValueError(f"distance: to must be background or foreground, got {to!r}")
+    return to == "foreground"
+
+
+def _radius(radius):
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError(f"distance: the radius must be a number, got {radius!r}")
+    return int(_builder(C.check_radius, float(radius)))
+
+
+def _device_distance(xc, W, H, to_fg, mode, t=0):
+    """One transform of a device mask on torch's current stream: the int32 plane (squared) or a u8 plane."""
+    out = torch.empty((H, W), dtype=torch.int32 if mode == "squared" else torch.uint8, device=xc.device)
+    with torch.cuda.device(xc.device):
+        stream = torch.cuda.current_stream(xc.device)
+        _builder(C.distance_device, xc.data_ptr(), xc.stride(0) if H > 1 else W, W, H, to_fg, _DISTANCE_MODE[mode], t,
+                 out.data_ptr(), W, stream.cuda_stream)
+    # keep the input alive until the stream has consumed it
+    xc.record_stream(stream)
+    return out
+
+
+def distance_transform(x, to: str = "background", output: str = "squared"):
+    """Exact Euclidean distance transform of a mask.
+
+    x: HxW or HxWx1 uint8, sides up to 32767; a pixel is foreground iff it is != 0.  to="background"
+    (scipy.ndimage.distance_transform_edt's meaning): every pixel gets the distance to the nearest background
+    pixel, background pixels get 0; to="foreground" swaps the roles.  The frame edge is not a site.
+    output="squared": int32 d^2, DISTANCE_NONE everywhere in a frame without any site; "u8":
+    min(255, floor(d)); "float": float32 d (sqrt in float64, rounded; +inf without a site).  The result is HxW.
+    A CUDA tensor runs on the k_edt_* HIP kernels on torch's current stream without any synchronisation and
+    gives a CUDA tensor; numpy arrays / CPU tensors run on the threaded host executor and keep their container.
+    squared and u8 are bit-identical to `distance_transform_reference`."""
+    W, H = _distance_shape(x)
+    to_fg = _distance_to(to)
+    if output not in DISTANCE_OUTPUTS:
+        raise ValueError(f"distance: output must be one of {', '.join(DISTANCE_OUTPUTS)}, got {output!r}")
+    if _is_tensor(x) and x.is_cuda:
+        xc = _device_mask(x, W)
+        if output == "u8":
+            return _device_distance(xc, W, H, to_fg, "u8")
+        d2 = _device_distance(xc, W, H, to_fg, "squared")
+        if output == "squared":
+            return d2
+        d = d2.to(torch.float64).sqrt().to(torch.float32)
+        return torch.where(d2 == DISTANCE_NONE, torch.full_like(d, float("inf")), d)
+    a = _host_mask(x)
+    if output == "u8":
+        out = _builder(C.cpu_distance_u8, a, to_fg)
+    else:
+        out = _builder(C.cpu_distance, a, to_fg)
+        if output == "float":
+            out = _distance_float(out)
+    return torch.from_numpy(out) if _is_tensor(x) else out
+
+
+def _distance_float(d2):
+    d = np.sqrt(d2.astype(np.float64)).astype(np.float32)
+    d[d2 == DISTANCE_NONE] = np.inf
+    return d
+
+
+def distance_transform_reference(x, to: str = "background", output: str = "squared"):
+    """Golden CPU result of `distance_transform` (numpy): column scans, then the minimum over every column by
+    brute force, O(W^2 H); for small frames."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _distance_shape(arr)
+    to_fg = _distance_to(to)
+    if output not in DISTANCE_OUTPUTS:
+        raise ValueError(f"distance: output must be one of {', '.join(DISTANCE_OUTPUTS)}, got {output!r}")
+    if output == "u8":
+        return _builder(C.golden_distance_u8, _host_mask(arr), to_fg)
+    d2 = _builder(C.golden_distance, _host_mask(arr), to_fg)
+    return _distance_float(d2) if output == "float" else d2
+
+
+def _disk_morph(x, op, radius):
+    W, H = _distance_shape(x)
+    t = _radius(radius)
+    if _is_tensor(x) and x.is_cuda:
+        xc = _device_mask(x, W)
+        out = torch.empty((H, W), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            _builder(C.disk_morph_device, xc.data_ptr(), xc.stride(0) if H > 1 else W, W, H, op, t, out.data_ptr(), W,
+                     stream.cuda_stream)
+        xc.record_stream(stream)
+        return out[:, :, None] if x.ndim == 3 else out
+    out = _builder(C.cpu_disk_morph, _host_mask(x), op, float(radius))
+    if x.ndim == 3:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if _is_tensor(x) else out
+
+
+def erode_disk(x, radius):
+    """Erosion of a mask by the disc {dx^2 + dy^2 <= floor(radius^2)}: 255 where the whole disc lies in the
+    foreground (the frame edge does not erode), else 0; any radius >= 0 in a constant number of passes.  Shape and
+    container of x; radius 0 binarises."""
+    return _disk_morph(x, "erode", radius)
+
+
+def dilate_disk(x, radius):
+    """Dilation by the disc: 255 within radius of a foreground pixel, else 0."""
+    return _disk_morph(x, "dilate", radius)
+
+
+def open_disk(x, radius):
+    """dilate_disk(erode_disk(x, radius), radius): removes what is thinner than the disc."""
+    return _disk_morph(x, "open", radius)
+
+
+def close_disk(x, radius):
+    """erode_disk(dilate_disk(x, radius), radius): fills what is narrower than the disc."""
+    return _disk_morph(x, "close", radius)
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
+    C.distance_release_scratch()
 
 
 __all__ = [
@@ -1156,4 +1297,6 @@ __all__ = [
     "remap_reference", "MESH_SPACINGS",
     "label", "label_reference", "component_stats", "area_filter", "remove_small_objects", "keep_largest",
     "STAT_COLUMNS",
+    "distance_transform", "distance_transform_reference", "erode_disk", "dilate_disk", "open_disk", "close_disk",
+    "DISTANCE_NONE", "DISTANCE_OUTPUTS",
 ]

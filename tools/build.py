@@ -53,6 +53,7 @@ CORE_SOURCES = [
     "core/warp.cpp",
     "core/remap.cpp",
     "core/components.cpp",
+    "core/distance.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -71,6 +72,7 @@ CORE_SOURCES = [
     "hip/warp.hip",
     "hip/remap.hip",
     "hip/components.hip",
+    "hip/distance.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
