@@ -258,29 +258,36 @@ Input read_input(const std::string& path, bool device) {
   return in;
 }
 
+// One whole-frame stage on the device: `in` goes up, launch(src, dst, dst_pitch) queues the kernel on the null
+// stream, and the W2 x H2 result comes down.  The Buffers own the allocations, whatever throws.
+template <class Launch>
+Image device_stage(const Image& in, int W2, int H2, int device, Launch launch) {
+  HIP_CHECK(hipSetDevice(device));
+  Image out(W2, H2, in.C, NoInit{});
+  Buffer src(in.bytes(), true), dst(out.bytes(), true);
+  HIP_CHECK(hipMemcpy(src.data(), in.data.data(), in.bytes(), hipMemcpyHostToDevice));
+  launch(src.data(), dst.data(), out.row_bytes());
+  HIP_CHECK(hipMemcpy(out.data.data(), dst.data(), out.bytes(), hipMemcpyDeviceToHost));
+  return out;
+}
+
+// A JPEG's coefficients are decoded to pixels before a stage that works on pixels.
+void decode_pixels(Input* in) {
+  if (!in->coefs) return;
+  in->img = jpeg_pixels(std::move(in->jpeg));
+  in->jpeg = JpegCoefs{};
+  in->coefs = false;
+}
+
 // --resize WxH[:mode]: the frame is resized before the chain sees it (a stage in
 // front of the chain, like JPEG decode): on the GPU (k_resize) for device
 // backends, on cpu_resize for the host backend.
 Image resize_image(const Image& in, const ResizeSpec& r, bool on_device, int device) {
   if (!on_device) return cpu_resize(in, r.W, r.H, r.mode, cpu_threads());
   STRIPE_CHECK(r.W >= 1 && r.H >= 1, "resize: empty size");
-  HIP_CHECK(hipSetDevice(device));
-  Image out(r.W, r.H, in.C, NoInit{});
-  uint8_t *ds = nullptr, *dd = nullptr;
-  try {
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
-    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
-    resize_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), r.W, r.H, r.mode, nullptr);
-    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-  } catch (...) {
-    (void)hipFree(ds);
-    (void)hipFree(dd);
-    throw;
-  }
-  HIP_CHECK(hipFree(ds));
-  HIP_CHECK(hipFree(dd));
-  return out;
+  return device_stage(in, r.W, r.H, device, [&](const uint8_t* src, uint8_t* dst, int64_t dst_pitch) {
+    resize_device(src, in.row_bytes(), in.W, in.H, in.C, dst, dst_pitch, r.W, r.H, r.mode, nullptr);
+  });
 }
 
 // Applies --resize to the loaded input (a JPEG's coefficients are decoded to
@@ -289,11 +296,7 @@ std::string resize_input(const Args& a, Input* in, bool on_device, int device) {
   if (!a.has("resize")) return "";
   const ResizeSpec r = parse_resize_spec(a.get("resize"));
   const int W0 = in->W, H0 = in->H;
-  if (in->coefs) {
-    in->img = jpeg_pixels(std::move(in->jpeg));
-    in->jpeg = JpegCoefs{};
-    in->coefs = false;
-  }
+  decode_pixels(in);
   in->img = resize_image(in->img, r, on_device, device);
   in->W = in->img.W;
   in->H = in->img.H;
@@ -313,24 +316,11 @@ Orient orient_of(const Args& a, const std::string& path) {
 
 Image orient_image(const Image& in, Orient op, const CropRect& crop, bool on_device, int device) {
   if (!on_device) return cpu_orient(in, op, crop, cpu_threads());
-  HIP_CHECK(hipSetDevice(device));
   const bool t = orient_t(op);
-  Image out(crop.empty() ? (t ? in.H : in.W) : crop.w, crop.empty() ? (t ? in.W : in.H) : crop.h, in.C, NoInit{});
-  uint8_t *ds = nullptr, *dd = nullptr;
-  try {
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
-    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
-    orient_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), op, crop, nullptr);
-    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-  } catch (...) {
-    (void)hipFree(ds);
-    (void)hipFree(dd);
-    throw;
-  }
-  HIP_CHECK(hipFree(ds));
-  HIP_CHECK(hipFree(dd));
-  return out;
+  return device_stage(in, crop.empty() ? (t ? in.H : in.W) : crop.w, crop.empty() ? (t ? in.W : in.H) : crop.h, device,
+                      [&](const uint8_t* src, uint8_t* dst, int64_t dst_pitch) {
+                        orient_device(src, in.row_bytes(), in.W, in.H, in.C, dst, dst_pitch, op, crop, nullptr);
+                      });
 }
 
 // the --crop window, checked against the oriented frame of a W x H source
@@ -348,11 +338,7 @@ std::string orient_input(const Args& a, Input* in, const std::string& path, bool
   const Orient op = orient_of(a, path);
   const int W0 = in->W, H0 = in->H;
   const CropRect crop = crop_of(a, op, W0, H0);
-  if (in->coefs) {
-    in->img = jpeg_pixels(std::move(in->jpeg));
-    in->jpeg = JpegCoefs{};
-    in->coefs = false;
-  }
+  decode_pixels(in);
   in->img = orient_image(in->img, op, crop, on_device, device);
   in->W = in->img.W;
   in->H = in->img.H;
@@ -407,29 +393,12 @@ Image remap_image(const Image& in, const Mesh& me, const Args& a, bool on_device
   RemapMesh rm = me.view(parse_warp_mode(a.get("warp-mode", "bilinear")), border, fill);
   if (!on_device) return cpu_remap(in, rm, cpu_threads());
   HIP_CHECK(hipSetDevice(device));
-  Image out(me.W2, me.H2, in.C, NoInit{});
-  uint8_t *ds = nullptr, *dd = nullptr;
-  int32_t* dm = nullptr;
-  const size_t mesh_bytes = me.nodes.size() * sizeof(int32_t);
-  try {
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dm), mesh_bytes));
-    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dm, me.nodes.data(), mesh_bytes, hipMemcpyHostToDevice));
-    rm.nodes = dm;
-    remap_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), rm, (int64_t)me.nodes.size(), nullptr);
-    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-  } catch (...) {
-    (void)hipFree(ds);
-    (void)hipFree(dd);
-    (void)hipFree(dm);
-    throw;
-  }
-  HIP_CHECK(hipFree(ds));
-  HIP_CHECK(hipFree(dd));
-  HIP_CHECK(hipFree(dm));
-  return out;
+  Buffer nodes(me.nodes.size() * sizeof(int32_t), true);
+  HIP_CHECK(hipMemcpy(nodes.data(), me.nodes.data(), nodes.bytes(), hipMemcpyHostToDevice));
+  rm.nodes = reinterpret_cast<const int32_t*>(nodes.data());
+  return device_stage(in, me.W2, me.H2, device, [&](const uint8_t* src, uint8_t* dst, int64_t dst_pitch) {
+    remap_device(src, in.row_bytes(), in.W, in.H, in.C, dst, dst_pitch, rm, (int64_t)me.nodes.size(), nullptr);
+  });
 }
 
 WarpMap warp_map_of(const Args& a, int W, int H, std::string* token) {
@@ -451,23 +420,9 @@ WarpMap warp_map_of(const Args& a, int W, int H, std::string* token) {
 
 Image warp_image(const Image& in, const WarpMap& m, bool on_device, int device) {
   if (!on_device) return cpu_warp(in, m, cpu_threads());
-  HIP_CHECK(hipSetDevice(device));
-  Image out(m.W2, m.H2, in.C, NoInit{});
-  uint8_t *ds = nullptr, *dd = nullptr;
-  try {
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), in.bytes()));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), out.bytes()));
-    HIP_CHECK(hipMemcpy(ds, in.data.data(), in.bytes(), hipMemcpyHostToDevice));
-    warp_device(ds, in.row_bytes(), in.W, in.H, in.C, dd, out.row_bytes(), m, nullptr);
-    HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-  } catch (...) {
-    (void)hipFree(ds);
-    (void)hipFree(dd);
-    throw;
-  }
-  HIP_CHECK(hipFree(ds));
-  HIP_CHECK(hipFree(dd));
-  return out;
+  return device_stage(in, m.W2, m.H2, device, [&](const uint8_t* src, uint8_t* dst, int64_t dst_pitch) {
+    warp_device(src, in.row_bytes(), in.W, in.H, in.C, dst, dst_pitch, m, nullptr);
+  });
 }
 
 // Applies --rotate / --warp to the loaded input (a JPEG's coefficients are
@@ -476,26 +431,41 @@ std::string warp_input(const Args& a, Input* in, bool on_device, int device) {
   if (!warp_requested(a)) return "";
   const int W0 = in->W, H0 = in->H;
   std::string token, extra;
-  auto pixels = [&] {
-    if (in->coefs) {
-      in->img = jpeg_pixels(std::move(in->jpeg));
-      in->jpeg = JpegCoefs{};
-      in->coefs = false;
-    }
-  };
   if (mesh_requested(a)) {
     const Mesh me = mesh_of(a, W0, H0, &token);
-    pixels();
+    decode_pixels(in);
     in->img = remap_image(in->img, me, a, on_device, device);
     extra = ",\"mesh_spacing\":" + std::to_string(me.spacing());
   } else {
     const WarpMap m = warp_map_of(a, W0, H0, &token);
-    pixels();
+    decode_pixels(in);
     in->img = warp_image(in->img, m, on_device, device);
   }
   in->W = in->img.W;
   in->H = in->img.H;
   return ",\"warped_from\":[" + std::to_string(W0) + "," + std::to_string(H0) + "],\"warp\":\"" + token + "\"" + extra;
+}
+
+// The geometry stages in front of the chain, in their order: orient / crop, warp, resize; returns the JSON
+// members of the stages that ran.
+std::string geometry_input(const Args& a, Input* in, const std::string& path, bool on_device, int device) {
+  std::string js = orient_input(a, in, path, on_device, device);
+  js += warp_input(a, in, on_device, device);
+  return js + resize_input(a, in, on_device, device);
+}
+
+// The same stages on the --held image, which is oriented, cropped, warped and resized the same way.
+Image geometry_held(const Args& a, Image held, const std::string& path, bool on_device, int device) {
+  if (a.has("orient") || a.has("crop")) {
+    const Orient op = orient_of(a, path);
+    held = orient_image(held, op, crop_of(a, op, held.W, held.H), on_device, device);
+  }
+  if (warp_requested(a)) {
+    if (mesh_requested(a)) held = remap_image(held, mesh_of(a, held.W, held.H, nullptr), a, on_device, device);
+    else held = warp_image(held, warp_map_of(a, held.W, held.H, nullptr), on_device, device);
+  }
+  if (a.has("resize")) held = resize_image(held, parse_resize_spec(a.get("resize")), on_device, device);
+  return held;
 }
 
 // One rank of a multi-process job: `stripe run --backend rccl --world N --rank r
@@ -513,9 +483,7 @@ int cmd_run_rank(const Args& a) {
   if (rank == 0) {
     STRIPE_CHECK(a.has("input") && a.has("output"), "rank 0 needs --input and --output");
     in = read_input(a.get("input"), true);
-    resized = orient_input(a, &in, a.get("input"), true, device);  // before the geometry is broadcast
-    resized += warp_input(a, &in, true, device);
-    resized += resize_input(a, &in, true, device);
+    resized = geometry_input(a, &in, a.get("input"), true, device);  // before the geometry is broadcast
     cfg = config_from(a, in.W, in.H, in.C);
   } else {
     cfg = config_from(a, 1, 1, 3);  // geometry arrives with the metadata broadcast
@@ -555,9 +523,7 @@ int cmd_run(const Args& a) {
   const auto tr = std::chrono::steady_clock::now();
   Input in = read_input(a.get("input"), !host_run);
   const std::vector<int> rdevs = parse_int_list(a.get("devices"));
-  const std::string resized = orient_input(a, &in, a.get("input"), !host_run, rdevs.empty() ? 0 : rdevs[0]) +
-                              warp_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]) +
-                              resize_input(a, &in, !host_run, rdevs.empty() ? 0 : rdevs[0]);
+  const std::string resized = geometry_input(a, &in, a.get("input"), !host_run, rdevs.empty() ? 0 : rdevs[0]);
   const double read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
   EngineConfig cfg = config_from(a, in.W, in.H, in.C);
   const int N = a.geti("ranks", 1);
@@ -572,19 +538,8 @@ int cmd_run(const Args& a) {
     // --held FILE: a second image of equal size as the external held image (the
     // two-image form of the combine ops): one engine, no scatter / gather
     STRIPE_CHECK(N == 1, "--held is single-process only (--ranks 1), got --ranks " << N);
-    Image held = read_image(a.get("held"));
-    if (a.has("orient") || a.has("crop")) {  // the held image is oriented and cropped the same way
-      const Orient hop = orient_of(a, a.get("held"));
-      held = orient_image(held, hop, crop_of(a, hop, held.W, held.H), !host_run, rdevs.empty() ? 0 : rdevs[0]);
-    }
-    if (warp_requested(a)) {  // the held image gets the same warp
-      if (mesh_requested(a))
-        held = remap_image(held, mesh_of(a, held.W, held.H, nullptr), a, !host_run, rdevs.empty() ? 0 : rdevs[0]);
-      else
-        held = warp_image(held, warp_map_of(a, held.W, held.H, nullptr), !host_run, rdevs.empty() ? 0 : rdevs[0]);
-    }
-    if (a.has("resize"))  // the held image is resized the same way
-      held = resize_image(held, parse_resize_spec(a.get("resize")), !host_run, rdevs.empty() ? 0 : rdevs[0]);
+    const Image held =
+        geometry_held(a, read_image(a.get("held")), a.get("held"), !host_run, rdevs.empty() ? 0 : rdevs[0]);
     const Image cur = in.coefs ? jpeg_pixels(JpegCoefs(in.jpeg)) : in.img;
     STRIPE_CHECK(held.W == cur.W && held.H == cur.H && held.C == cur.C,
                  "--held image is " << held.W << "x" << held.H << "x" << held.C << ", the input " << cur.W << "x"
@@ -667,9 +622,7 @@ int cmd_convert(const Args& a) {
   in.W = in.img.W, in.H = in.img.H, in.C = in.img.C;
   const bool host_run = a.get("backend", device_count() > 0 ? "local" : "host") == "host";
   const std::vector<int> devs = parse_int_list(a.get("devices"));
-  const std::string resized = orient_input(a, &in, a.get("input"), !host_run, devs.empty() ? 0 : devs[0]) +
-                              warp_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]) +
-                              resize_input(a, &in, !host_run, devs.empty() ? 0 : devs[0]);
+  const std::string resized = geometry_input(a, &in, a.get("input"), !host_run, devs.empty() ? 0 : devs[0]);
   const Image& img = in.img;
   write_image(a.get("output"), img, a.geti("quality", 95));
   std::printf("{\"cmd\":\"convert\",\"W\":%d,\"H\":%d,\"C\":%d%s}\n", img.W, img.H, img.C, resized.c_str());
@@ -715,29 +668,17 @@ int cmd_label(const Args& a) {
     }
   } else {
     HIP_CHECK(hipSetDevice(device));
-    uint8_t *ds = nullptr, *dd = nullptr;
-    int32_t* dl = nullptr;
-    int64_t* dt = nullptr;
-    try {
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), img.bytes()));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), img.bytes()));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dl), img.bytes() * sizeof(int32_t)));
-      HIP_CHECK(hipMemcpy(ds, img.data.data(), img.bytes(), hipMemcpyHostToDevice));
-      N = components_device(ds, W, W, H, conn, dl, W, nullptr);
-      tab.resize((size_t)(N + 1) * kStatCols);
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tab.size() * sizeof(int64_t)));
-      component_stats_device(dl, W, W, H, N, dt, nullptr);
-      area_filter_device(ds, W, W, H, dl, W, dt, N, amin, amax, dd, W, nullptr);
-      HIP_CHECK(hipMemcpy(tab.data(), dt, tab.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-    } catch (...) {
-      (void)hipFree(ds), (void)hipFree(dd), (void)hipFree(dl), (void)hipFree(dt);
-      throw;
-    }
-    HIP_CHECK(hipFree(ds));
-    HIP_CHECK(hipFree(dd));
-    HIP_CHECK(hipFree(dl));
-    HIP_CHECK(hipFree(dt));
+    Buffer ds(img.bytes(), true), dd(img.bytes(), true), labels(img.bytes() * sizeof(int32_t), true);
+    int32_t* dl = reinterpret_cast<int32_t*>(labels.data());
+    HIP_CHECK(hipMemcpy(ds.data(), img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+    N = components_device(ds.data(), W, W, H, conn, dl, W, nullptr);
+    tab.resize((size_t)(N + 1) * kStatCols);
+    Buffer table(tab.size() * sizeof(int64_t), true);
+    int64_t* dt = reinterpret_cast<int64_t*>(table.data());
+    component_stats_device(dl, W, W, H, N, dt, nullptr);
+    area_filter_device(ds.data(), W, W, H, dl, W, dt, N, amin, amax, dd.data(), W, nullptr);
+    HIP_CHECK(hipMemcpy(tab.data(), dt, table.bytes(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out.data.data(), dd.data(), out.bytes(), hipMemcpyDeviceToHost));
   }
   if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
   if (a.has("stats")) {
@@ -805,27 +746,15 @@ int cmd_distance(const Args& a) {
       for (size_t p = 0; p < d2.size(); ++p) out.data[p] = distance_u8(d2[p]);
   } else {
     HIP_CHECK(hipSetDevice(device));
-    uint8_t *ds = nullptr, *dd = nullptr;
-    int32_t* dq = nullptr;
-    try {
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), img.bytes()));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), img.bytes()));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dq), img.bytes() * sizeof(int32_t)));
-      HIP_CHECK(hipMemcpy(ds, img.data.data(), img.bytes(), hipMemcpyHostToDevice));
-      distance_device(ds, W, W, H, to_fg, (int)DistanceMode::Squared, 0, dq, W, nullptr);
-      if (nops)
-        disk_morph_device(ds, W, W, H, (int)op, t, dd, W, nullptr);
-      else
-        distance_device(ds, W, W, H, to_fg, (int)DistanceMode::U8, 0, dd, W, nullptr);
-      HIP_CHECK(hipMemcpy(d2.data(), dq, d2.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
-    } catch (...) {
-      (void)hipFree(ds), (void)hipFree(dd), (void)hipFree(dq);
-      throw;
-    }
-    HIP_CHECK(hipFree(ds));
-    HIP_CHECK(hipFree(dd));
-    HIP_CHECK(hipFree(dq));
+    Buffer ds(img.bytes(), true), dd(img.bytes(), true), dq(img.bytes() * sizeof(int32_t), true);
+    HIP_CHECK(hipMemcpy(ds.data(), img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+    distance_device(ds.data(), W, W, H, to_fg, (int)DistanceMode::Squared, 0, dq.data(), W, nullptr);
+    if (nops)
+      disk_morph_device(ds.data(), W, W, H, (int)op, t, dd.data(), W, nullptr);
+    else
+      distance_device(ds.data(), W, W, H, to_fg, (int)DistanceMode::U8, 0, dd.data(), W, nullptr);
+    HIP_CHECK(hipMemcpy(d2.data(), dq.data(), dq.bytes(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out.data.data(), dd.data(), out.bytes(), hipMemcpyDeviceToHost));
   }
   if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
   int32_t top = -1;

@@ -11,41 +11,9 @@
 
 namespace stripe {
 
+using namespace spec;  // parse_number, parse_uint, num (warp.h)
+
 namespace {
-// all of s as a decimal number or inf / nan (which the callers refuse by name); as warp.cpp's
-bool parse_number(const std::string& s, double* v) {
-  if (s.empty() || s.size() > 64) return false;
-  for (char c : s)
-    if (c == 'x' || c == 'X' || c == 'p' || c == 'P' || std::isspace((unsigned char)c)) return false;
-  char* end = nullptr;
-  *v = std::strtod(s.c_str(), &end);
-  return end == s.c_str() + s.size();
-}
-
-int parse_uint(const std::string& s) {
-  if (s.empty() || s.size() > 5) return -1;
-  int v = 0;
-  for (char c : s) {
-    if (c < '0' || c > '9') return -1;
-    v = v * 10 + (c - '0');
-  }
-  return v <= kWarpMaxSize ? v : -1;
-}
-
-// the shortest decimal form that reads back exactly (as warp.cpp's)
-std::string num(double v) {
-  char buf[40];
-  std::snprintf(buf, sizeof buf, "%.17g", v);
-  double back = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int p = 1; p < 17; ++p) {
-      char t[40];
-      std::snprintf(t, sizeof t, "%.*g", p, v);
-      if ((pass == 1 || !std::strchr(t, 'e')) && parse_number(t, &back) && back == v) return t;
-    }
-  return buf;
-}
-
 // "a<sep>b<sep>...": between lo and hi numbers
 bool split_numbers(const std::string& s, char sep, int lo, int hi, std::vector<double>* out) {
   out->clear();

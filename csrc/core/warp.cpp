@@ -13,9 +13,7 @@
 
 namespace stripe {
 
-namespace {
-// all of s as a decimal number (digits, sign, point, exponent) or inf / nan, which the callers
-// refuse by name; false for anything else (hexadecimal floats and white space included)
+namespace spec {
 bool parse_number(const std::string& s, double* v) {
   if (s.empty() || s.size() > 64) return false;
   for (char c : s)
@@ -25,7 +23,6 @@ bool parse_number(const std::string& s, double* v) {
   return end == s.c_str() + s.size();
 }
 
-// all of s as a decimal integer in [0, kWarpMaxSize]; -1 otherwise
 int parse_uint(const std::string& s) {
   if (s.empty() || s.size() > 5) return -1;
   int v = 0;
@@ -40,7 +37,6 @@ std::string num(double v) {
   char buf[40];
   std::snprintf(buf, sizeof buf, "%.17g", v);
   double back = 0;
-  // the shortest form that reads back exactly, without an exponent where there is one
   for (int pass = 0; pass < 2; ++pass)
     for (int p = 1; p < 17; ++p) {
       char t[40];
@@ -49,7 +45,11 @@ std::string num(double v) {
     }
   return buf;
 }
+}  // namespace spec
 
+using namespace spec;
+
+namespace {
 inline uint8_t tap(const Image& in, int iy, int ix, int ch, const WarpMap& m) {
   if (m.border == WarpBorder::Replicate) {
     iy = std::min(std::max(iy, 0), in.H - 1);

@@ -100,17 +100,58 @@ void launch_histogram(const HistLaunch& L, hipStream_t s) {
   launch_hist_kernel(L, s);
 }
 
+namespace {
+
+// One pitched view of a whole-frame launch: h rows of w pixels of px bytes, `pitch` bytes apart; base / bytes
+// name the allocation it lies in where the caller knows it.  `name` and `rows` word the messages.
+struct View {
+  const char *name, *rows;
+  const void* p;
+  int64_t pitch;
+  int w, h, px;
+  const uint8_t* base;
+  int64_t bytes;
+};
+
+void check_pitch(const char* op, const View& v) {
+  STRIPE_CHECK(v.pitch >= (int64_t)v.w * v.px,
+               op << ": " << v.name << "_pitch " << v.pitch << " < row bytes " << (int64_t)v.w * v.px);
+}
+
+// the kernels address with 64-bit pointers: no size limit beyond the axes'.  Where the caller names the
+// allocation, the rows touched lie inside it.
+void check_inside(const char* op, const View& v) {
+  const uint8_t* p = static_cast<const uint8_t*>(v.p);
+  if (v.base)
+    STRIPE_CHECK(p >= v.base && (p - v.base) + (int64_t)(v.h - 1) * v.pitch + (int64_t)v.w * v.px <= v.bytes,
+                 op << ": " << v.rows << " rows outside their buffer");
+}
+
+// The checks every geometry stage makes on its two views before the kernel touches memory.
+void check_frame(const char* op, int C, int max_size, const View& src, const View& dst) {
+  STRIPE_CHECK(src.p && dst.p, "bad " << op << " launch: null src or dst");
+  STRIPE_CHECK(C == 1 || C == 3, op << " needs 1 or 3 channels, got C = " << C);
+  for (const View* v : {&src, &dst})
+    STRIPE_CHECK(v->w >= 1 && v->w <= max_size && v->h >= 1 && v->h <= max_size,
+                 op << ": " << v->rows << " size " << v->w << "x" << v->h << " outside 1.." << max_size);
+  check_pitch(op, src);
+  check_pitch(op, dst);
+  check_inside(op, src);
+  check_inside(op, dst);
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+}
+
+// the two views of a *Launch with the geometry stages' field names
+template <class L>
+void check_frame(const char* op, int max_size, const L& l, int W, int H, int W2, int H2) {
+  check_frame(op, l.C, max_size, {"src", "source", l.src, l.src_pitch, W, H, l.C, l.src_base, l.src_bytes},
+              {"dst", "destination", l.dst, l.dst_pitch, W2, H2, l.C, l.dst_base, l.dst_bytes});
+}
+
+}  // namespace
+
 void launch_resize(const ResizeLaunch& L, hipStream_t s) {
-  // host-side shape checks before the kernel touches memory
-  STRIPE_CHECK(L.src && L.dst, "bad resize launch: null src or dst");
-  STRIPE_CHECK(L.C == 1 || L.C == 3, "resize needs 1 or 3 channels, got C = " << L.C);
-  STRIPE_CHECK(L.W >= 1 && L.W <= kResizeMaxSize && L.H >= 1 && L.H <= kResizeMaxSize,
-               "resize: source size " << L.W << "x" << L.H << " outside 1.." << kResizeMaxSize);
-  STRIPE_CHECK(L.W2 >= 1 && L.W2 <= kResizeMaxSize && L.H2 >= 1 && L.H2 <= kResizeMaxSize,
-               "resize: destination size " << L.W2 << "x" << L.H2 << " outside 1.." << kResizeMaxSize);
-  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "resize: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
-  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W2 * L.C,
-               "resize: dst_pitch " << L.dst_pitch << " < row bytes " << L.W2 * L.C);
+  check_frame("resize", kResizeMaxSize, L, L.W, L.H, L.W2, L.H2);
   STRIPE_CHECK(L.fx && L.ox && L.wx && L.fy && L.oy && L.wy, "resize: missing tap tables");
   // the tile plan fits the instance it names (the kernel's LDS arrays)
   STRIPE_CHECK(L.cls >= 0 && L.cls < 4 && L.tile >= 4 && L.tile <= kResizeTile && L.tile % 4 == 0,
@@ -120,55 +161,18 @@ void launch_resize(const ResizeLaunch& L, hipStream_t s) {
                "resize: a tile's source span of " << L.max_span << " bytes does not fit class " << L.cls);
   STRIPE_CHECK(rc.w_entries == 0 ? L.max_count_x <= 2 : L.max_weights <= rc.w_entries,
                "resize: a tile's x-weights do not fit class " << L.cls);
-  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
-  // Where the caller names the allocations, the rows touched lie inside them.
-  if (L.src_base)
-    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
-                                            L.src_bytes,
-                 "resize: source rows outside their buffer");
-  if (L.dst_base)
-    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(L.H2 - 1) * L.dst_pitch +
-                                                (int64_t)L.W2 * L.C <= L.dst_bytes,
-                 "resize: destination rows outside their buffer");
-  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
   launch_resize_kernel(L, s);
 }
 
 void launch_orient(const OrientLaunch& L, hipStream_t s) {
-  // host-side shape checks before the kernel touches memory
-  STRIPE_CHECK(L.src && L.dst, "bad orient launch: null src or dst");
-  STRIPE_CHECK(L.C == 1 || L.C == 3, "orient needs 1 or 3 channels, got C = " << L.C);
-  STRIPE_CHECK(L.w >= 1 && L.w <= kOrientMaxSize && L.h >= 1 && L.h <= kOrientMaxSize,
-               "orient: source size " << L.w << "x" << L.h << " outside 1.." << kOrientMaxSize);
   STRIPE_CHECK((int)L.op >= 0 && (int)L.op < 8, "orient: bad orientation " << (int)L.op);
-  const int W2 = orient_t(L.op) ? L.h : L.w, H2 = orient_t(L.op) ? L.w : L.h;
-  STRIPE_CHECK(L.src_pitch >= (int64_t)L.w * L.C, "orient: src_pitch " << L.src_pitch << " < row bytes " << L.w * L.C);
-  STRIPE_CHECK(L.dst_pitch >= (int64_t)W2 * L.C, "orient: dst_pitch " << L.dst_pitch << " < row bytes " << W2 * L.C);
-  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
-  // Where the caller names the allocations, the rows touched lie inside them.
-  if (L.src_base)
-    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.h - 1) * L.src_pitch + (int64_t)L.w * L.C <=
-                                            L.src_bytes,
-                 "orient: source rows outside their buffer");
-  if (L.dst_base)
-    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(H2 - 1) * L.dst_pitch + (int64_t)W2 * L.C <=
-                                            L.dst_bytes,
-                 "orient: destination rows outside their buffer");
-  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  check_frame("orient", kOrientMaxSize, L, L.w, L.h, orient_t(L.op) ? L.h : L.w, orient_t(L.op) ? L.w : L.h);
   launch_orient_kernel(L, s);
 }
 
 void launch_warp(const WarpLaunch& L, hipStream_t s) {
-  // host-side shape checks before the kernel touches memory
-  STRIPE_CHECK(L.src && L.dst, "bad warp launch: null src or dst");
-  STRIPE_CHECK(L.C == 1 || L.C == 3, "warp needs 1 or 3 channels, got C = " << L.C);
-  STRIPE_CHECK(L.W >= 1 && L.W <= kWarpMaxSize && L.H >= 1 && L.H <= kWarpMaxSize,
-               "warp: source size " << L.W << "x" << L.H << " outside 1.." << kWarpMaxSize);
   const WarpMap& m = L.map;
-  STRIPE_CHECK(m.W2 >= 1 && m.W2 <= kWarpMaxSize && m.H2 >= 1 && m.H2 <= kWarpMaxSize,
-               "warp: destination size " << m.W2 << "x" << m.H2 << " outside 1.." << kWarpMaxSize);
-  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "warp: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
-  STRIPE_CHECK(L.dst_pitch >= (int64_t)m.W2 * L.C, "warp: dst_pitch " << L.dst_pitch << " < row bytes " << m.W2 * L.C);
+  check_frame("warp", kWarpMaxSize, L, L.W, L.H, m.W2, m.H2);
   // the quantiser's ranges: every term of the map stays below 2^48
   for (int i = 0; i < 2; ++i) {
     STRIPE_CHECK(m.A[i][0] > -(int64_t(64) << kWarpQ) && m.A[i][0] < (int64_t(64) << kWarpQ) &&
@@ -179,62 +183,30 @@ void launch_warp(const WarpLaunch& L, hipStream_t s) {
   }
   STRIPE_CHECK((int)m.mode >= 0 && (int)m.mode < 2 && (int)m.border >= 0 && (int)m.border < 2,
                "warp: bad mode or border");
-  // the kernel addresses with 64-bit pointers: no size limit beyond the axes'.
-  // Where the caller names the allocations, the rows touched lie inside them.
-  if (L.src_base)
-    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
-                                            L.src_bytes,
-                 "warp: source rows outside their buffer");
-  if (L.dst_base)
-    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(m.H2 - 1) * L.dst_pitch +
-                                                (int64_t)m.W2 * L.C <= L.dst_bytes,
-                 "warp: destination rows outside their buffer");
-  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
   launch_warp_kernel(L, s);
 }
 
 void launch_remap(const RemapLaunch& L, hipStream_t s) {
-  // host-side shape checks before the kernel touches memory (the nodes themselves stay on the device: the
-  // kernel clamps or tests every index that follows from them)
-  STRIPE_CHECK(L.src && L.dst, "bad remap launch: null src or dst");
-  STRIPE_CHECK(L.C == 1 || L.C == 3, "remap needs 1 or 3 channels, got C = " << L.C);
-  STRIPE_CHECK(L.W >= 1 && L.W <= kWarpMaxSize && L.H >= 1 && L.H <= kWarpMaxSize,
-               "remap: source size " << L.W << "x" << L.H << " outside 1.." << kWarpMaxSize);
+  // (the nodes themselves stay on the device: the kernel clamps or tests every index that follows from them)
   const RemapMesh& m = L.mesh;
-  check_mesh(m, L.mesh_count, false, "launch");
-  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W * L.C, "remap: src_pitch " << L.src_pitch << " < row bytes " << L.W * L.C);
-  STRIPE_CHECK(L.dst_pitch >= (int64_t)m.W2 * L.C, "remap: dst_pitch " << L.dst_pitch << " < row bytes " << m.W2 * L.C);
+  check_mesh(m, L.mesh_count, false, "launch");  // (and with it the destination's size)
+  check_frame("remap", kWarpMaxSize, L, L.W, L.H, m.W2, m.H2);
   STRIPE_CHECK((reinterpret_cast<uintptr_t>(m.nodes) & 3) == 0, "remap: the mesh must be aligned to 4 bytes");
-  if (L.src_base)
-    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W * L.C <=
-                                            L.src_bytes,
-                 "remap: source rows outside their buffer");
-  if (L.dst_base)
-    STRIPE_CHECK(L.dst >= L.dst_base && (L.dst - L.dst_base) + (int64_t)(m.H2 - 1) * L.dst_pitch +
-                                                (int64_t)m.W2 * L.C <= L.dst_bytes,
-                 "remap: destination rows outside their buffer");
-  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
   launch_remap_kernel(L, s);
 }
 
 int launch_components(const ComponentsLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
+  const View src{"src", "source", L.src, L.src_pitch, L.W, L.H, 1, L.src_base, L.src_bytes};
+  const View labels{"labels", "label", L.labels, L.labels_pitch * 4, L.W, L.H, 4, L.labels_base, L.labels_bytes};
   STRIPE_CHECK(L.src && L.labels, "bad components launch: null src or labels");
   check_components(L.W, L.H, 1, L.conn);
-  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "components: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  check_pitch("components", src);
   STRIPE_CHECK(L.labels_pitch >= (int64_t)L.W,
                "components: labels_pitch " << L.labels_pitch << " < the row's " << L.W << " elements");
   STRIPE_CHECK((reinterpret_cast<uintptr_t>(L.labels) & 3) == 0, "components: the labels must be aligned to 4 bytes");
-  if (L.src_base)
-    STRIPE_CHECK(L.src >= L.src_base && (L.src - L.src_base) + (int64_t)(L.H - 1) * L.src_pitch + (int64_t)L.W <=
-                                            L.src_bytes,
-                 "components: source rows outside their buffer");
-  if (L.labels_base) {
-    const uint8_t* lb = reinterpret_cast<const uint8_t*>(L.labels);
-    STRIPE_CHECK(lb >= L.labels_base && (lb - L.labels_base) + ((int64_t)(L.H - 1) * L.labels_pitch + L.W) * 4 <=
-                                            L.labels_bytes,
-                 "components: label rows outside their buffer");
-  }
+  check_inside("components", src);
+  check_inside("components", labels);
   (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
   return launch_components_kernels(L, s);
 }

@@ -97,6 +97,16 @@ RotateSpec parse_rotate_spec(const std::string& token);
 // The canonical tokens the CLIs report: "rotate:DEG:same|fit", "affine:a;b;c;d;e;f:WxH".
 std::string rotate_token(const RotateSpec& r);
 std::string warp_token(const WarpSpec& s, int W2, int H2);
+// The number handling of these specs and of the mesh warp's (remap.h).
+namespace spec {
+// all of s as a decimal number (digits, sign, point, exponent) or inf / nan, which the callers
+// refuse by name; false for anything else (hexadecimal floats and white space included)
+bool parse_number(const std::string& s, double* v);
+// all of s as a decimal integer in [0, kWarpMaxSize]; -1 otherwise
+int parse_uint(const std::string& s);
+// the shortest decimal form that reads back exactly, without an exponent where there is one
+std::string num(double v);
+}  // namespace spec
 
 // Source coordinates of one output pixel (shared by all layers).
 inline int64_t warp_sx(const WarpMap& m, int x, int y) { return (int64_t)m.A[0][0] * x + (int64_t)m.A[0][1] * y + m.B[0]; }

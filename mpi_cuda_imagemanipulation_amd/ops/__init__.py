@@ -410,6 +410,64 @@ def maximum(x, y):
     return combine(x, y, "max")
 
 
+# ---- whole-frame stages in front of the chain: one driver for resize, orient, warp and remap ----
+def _packed_frame(arr, fn):
+    """fn on arr as the packed array the C++ layer takes (HxWx1 goes in as HxW); the result keeps arr's rank."""
+    keep = arr.ndim == 3 and arr.shape[2] == 1
+    out = fn(np.ascontiguousarray(arr[:, :, 0] if keep else arr))
+    return out[:, :, None] if keep else out
+
+
+def _reference_frame(x, golden):
+    """The golden loop of a stage on x as a numpy array: golden(W, H) gives the function of the packed array."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    W, H, _ = _shape(arr)
+    return _packed_frame(arr, golden(W, H))
+
+
+def _frame_stage(x, plan, on_device, on_host, pitched=True):
+    """One frame, or a BxHxWxC batch frame by frame, through a whole-frame stage.
+
+    plan(W, H) -> (W2, H2, args): the destination size and whatever the two calls need.
+    on_device(view, W2, H2, args, stream) makes the C.*_device call on torch's current stream; view is its
+    leading arguments (src, src_pitch, W, H, C, dst, dst_pitch); it returns the tensors besides the input
+    that must outlive the queued work, or None.  pitched: the kernel reads a strided view in place as long
+    as a row's pixels are packed; otherwise the input is made contiguous.
+    on_host(arr, W2, H2, args) makes the C.cpu_* call on a packed numpy array.
+    The result has x's container and rank."""
+    if x.ndim == 4:
+        if x.shape[3] not in (1, 3):
+            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
+        outs = [_frame_stage(x[b], plan, on_device, on_host, pitched) for b in range(x.shape[0])]
+        if outs:
+            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
+        W2, H2, _ = plan(x.shape[2], x.shape[1])
+        shape = (0, H2, W2, x.shape[3])
+        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
+    W, H, Cc = _shape(x)
+    W2, H2, args = plan(W, H)
+    if _is_tensor(x) and x.is_cuda:
+        if x.dtype != torch.uint8:
+            raise TypeError("image tensor must be uint8")
+        packed = pitched and x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
+        xc = x if packed else x.contiguous()
+        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            view = (xc.data_ptr(), xc.stride(0) if pitched else W * Cc, W, H, Cc, out.data_ptr(), W2 * Cc)
+            extra = on_device(view, W2, H2, args, stream) or ()
+        # keep the input (and the stage's own tensors) alive until the stream has consumed them
+        for t in (xc, *extra):
+            t.record_stream(stream)
+        return out
+    was_tensor = _is_tensor(x)
+    arr = x.numpy() if was_tensor else np.asarray(x)
+    if arr.dtype != np.uint8:
+        raise TypeError("image must be uint8")
+    out = _packed_frame(arr, lambda a: on_host(a, W2, H2, args))
+    return torch.from_numpy(out) if was_tensor else out
+
+
 # ---- resize: a stage in front of the chain, not a chain token ---------------------
 RESIZE_MODES = ("auto", "nearest", "bilinear", "area")
 _MAX_SIZE = 65535
@@ -443,47 +501,21 @@ def resize(x, size=None, scale=None, mode: str = "auto"):
     bit-identical to `resize_reference`.  A BxHxWxC batch runs frame by frame."""
     if mode not in RESIZE_MODES:
         raise ValueError(f"mode must be one of {RESIZE_MODES}, got {mode!r}")
-    if x.ndim == 4:
-        if x.shape[3] not in (1, 3):
-            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
-        H2, W2 = _resize_target(x.shape[1], x.shape[2], size, scale)
-        outs = [resize(x[b], (H2, W2), None, mode) for b in range(x.shape[0])]
-        if _is_tensor(x):
-            return torch.stack(outs) if outs else x.new_empty((0, H2, W2, x.shape[3]))
-        return np.stack(outs) if outs else np.empty((0, H2, W2, x.shape[3]), np.uint8)
-    W, H, Cc = _shape(x)
-    H2, W2 = _resize_target(H, W, size, scale)
-    if _is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.uint8:
-            raise TypeError("image tensor must be uint8")
-        xc = x.contiguous()
-        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device)
-            C.resize_device(xc.data_ptr(), W * Cc, W, H, Cc, out.data_ptr(), W2 * Cc, W2, H2, mode,
-                            stream.cuda_stream)
-        # keep the input alive until the stream has consumed it
-        xc.record_stream(stream)
-        return out
-    was_tensor = _is_tensor(x)
-    arr = x.numpy() if was_tensor else np.asarray(x)
-    if arr.dtype != np.uint8:
-        raise TypeError("image must be uint8")
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.cpu_resize(np.ascontiguousarray(arr[:, :, 0] if keep else arr), W2, H2, mode)
-    if keep:
-        out = out[:, :, None]
-    return torch.from_numpy(out) if was_tensor else out
+
+    def plan(W, H):
+        H2, W2 = _resize_target(H, W, size, scale)
+        return W2, H2, None
+    return _frame_stage(x, plan,
+                        lambda view, W2, H2, _, stream: C.resize_device(*view, W2, H2, mode, stream.cuda_stream),
+                        lambda arr, W2, H2, _: C.cpu_resize(arr, W2, H2, mode), pitched=False)
 
 
 def resize_reference(x, size=None, scale=None, mode: str = "auto"):
     """Golden CPU result of `resize`: the rule as a plain per-pixel loop."""
-    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-    W, H, _ = _shape(arr)
-    H2, W2 = _resize_target(H, W, size, scale)
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.golden_resize(np.ascontiguousarray(arr[:, :, 0] if keep else arr), W2, H2, mode)
-    return out[:, :, None] if keep else out
+    def golden(W, H):
+        H2, W2 = _resize_target(H, W, size, scale)
+        return lambda arr: C.golden_resize(arr, W2, H2, mode)
+    return _reference_frame(x, golden)
 
 
 # ---- orientation and crop: a stage in front of the chain, not a chain token ---------
@@ -521,48 +553,19 @@ def orient(x, op: str = "none", crop=None):
     `orient_reference`.  A BxHxWxC batch runs frame by frame."""
     name = C.parse_orient(op)[0]
     crop = _crop_tuple(crop)
-    if x.ndim == 4:
-        if x.shape[3] not in (1, 3):
-            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
-        outs = [orient(x[b], name, crop) for b in range(x.shape[0])]
-        if outs:
-            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
-        shape = (0,) + _oriented_shape(x.shape[1], x.shape[2], name, crop) + (x.shape[3],)
-        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
-    W, H, Cc = _shape(x)
-    H2, W2 = _oriented_shape(H, W, name, crop)
-    if _is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.uint8:
-            raise TypeError("image tensor must be uint8")
-        # the kernel takes pitched views: only the pixels of a row must be packed
-        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
-        xc = x if packed else x.contiguous()
-        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device)
-            C.orient_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, name, crop,
-                            stream.cuda_stream)
-        # keep the input alive until the stream has consumed it
-        xc.record_stream(stream)
-        return out
-    was_tensor = _is_tensor(x)
-    arr = x.numpy() if was_tensor else np.asarray(x)
-    if arr.dtype != np.uint8:
-        raise TypeError("image must be uint8")
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.cpu_orient(np.ascontiguousarray(arr[:, :, 0] if keep else arr), name, crop)
-    if keep:
-        out = out[:, :, None]
-    return torch.from_numpy(out) if was_tensor else out
+
+    def plan(W, H):
+        H2, W2 = _oriented_shape(H, W, name, crop)
+        return W2, H2, None
+    return _frame_stage(x, plan,
+                        lambda view, W2, H2, _, stream: C.orient_device(*view, name, crop, stream.cuda_stream),
+                        lambda arr, W2, H2, _: C.cpu_orient(arr, name, crop))
 
 
 def orient_reference(x, op: str = "none", crop=None):
     """Golden CPU result of `orient`: the rule as a plain per-pixel loop."""
-    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-    _shape(arr)
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.golden_orient(np.ascontiguousarray(arr[:, :, 0] if keep else arr), C.parse_orient(op)[0], _crop_tuple(crop))
-    return out[:, :, None] if keep else out
+    return _reference_frame(
+        x, lambda W, H: lambda arr: C.golden_orient(arr, C.parse_orient(op)[0], _crop_tuple(crop)))
 
 
 def flip(x, axis):
@@ -604,7 +607,7 @@ WARP_BORDERS = ("constant", "replicate")
 
 
 def _warp_map(W, H, M, size, inverse):
-    """The quantised map of a 2x3 matrix: ([A00, A01, B0, A10, A11, B1], W2, H2)."""
+    """The quantised map of a 2x3 matrix: (W2, H2, [A00, A01, B0, A10, A11, B1])."""
     try:
         vals = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(-1)]
     except (TypeError, ValueError):
@@ -624,7 +627,7 @@ def _warp_map(W, H, M, size, inverse):
         q = C.warp_quantise(vals, bool(inverse), W, H, W2, H2)
     except RuntimeError as e:
         raise ValueError(str(e)) from None
-    return list(q[:6]), q[6], q[7]
+    return q[6], q[7], list(q[:6])
 
 
 def _warp_args(mode, border, fill):
@@ -638,41 +641,11 @@ def _warp_args(mode, border, fill):
 
 
 def _warp_frame(x, mapper, mode, border, fill):
-    """One frame (or a batch, frame by frame) through k_warp / cpu_warp; mapper(W, H) -> (q, W2, H2)."""
-    if x.ndim == 4:
-        if x.shape[3] not in (1, 3):
-            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
-        outs = [_warp_frame(x[b], mapper, mode, border, fill) for b in range(x.shape[0])]
-        if outs:
-            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
-        _, W2, H2 = mapper(x.shape[2], x.shape[1])
-        shape = (0, H2, W2, x.shape[3])
-        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
-    W, H, Cc = _shape(x)
-    q, W2, H2 = mapper(W, H)
-    if _is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.uint8:
-            raise TypeError("image tensor must be uint8")
-        # the kernel takes pitched views: only the pixels of a row must be packed
-        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
-        xc = x if packed else x.contiguous()
-        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device)
-            C.warp_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, q, W2, H2, mode, border,
-                          fill, stream.cuda_stream)
-        # keep the input alive until the stream has consumed it
-        xc.record_stream(stream)
-        return out
-    was_tensor = _is_tensor(x)
-    arr = x.numpy() if was_tensor else np.asarray(x)
-    if arr.dtype != np.uint8:
-        raise TypeError("image must be uint8")
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.cpu_warp(np.ascontiguousarray(arr[:, :, 0] if keep else arr), q, W2, H2, mode, border, fill)
-    if keep:
-        out = out[:, :, None]
-    return torch.from_numpy(out) if was_tensor else out
+    """One frame (or a batch, frame by frame) through k_warp / cpu_warp; mapper(W, H) -> (W2, H2, q)."""
+    return _frame_stage(
+        x, mapper,
+        lambda view, W2, H2, q, stream: C.warp_device(*view, q, W2, H2, mode, border, fill, stream.cuda_stream),
+        lambda arr, W2, H2, q: C.cpu_warp(arr, q, W2, H2, mode, border, fill))
 
 
 def warp_affine(x, M, size=None, mode: str = "bilinear", border: str = "constant", fill: int = 0,
@@ -712,12 +685,10 @@ def warp_reference(x, M, size=None, mode: str = "bilinear", border: str = "const
                    inverse: bool = False):
     """Golden CPU result of `warp_affine`: the rule as a plain per-pixel loop."""
     mode, border, fill = _warp_args(mode, border, fill)
-    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-    W, H, _ = _shape(arr)
-    q, W2, H2 = _warp_map(W, H, M, size, inverse)
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.golden_warp(np.ascontiguousarray(arr[:, :, 0] if keep else arr), q, W2, H2, mode, border, fill)
-    return out[:, :, None] if keep else out
+    def golden(W, H):
+        W2, H2, q = _warp_map(W, H, M, size, inverse)
+        return lambda arr: C.golden_warp(arr, q, W2, H2, mode, border, fill)
+    return _reference_frame(x, golden)
 
 
 # ---- mesh warp: perspective, undistort, remap (the affine warp's slot in front of the chain) ----
@@ -773,48 +744,22 @@ def _check_mesh(mesh, spacing, W2, H2):
 
 
 def _remap_frame(x, mesher, mode, border, fill):
-    """One frame (or a batch, frame by frame) through k_remap / cpu_remap; mesher(W, H) -> (mesh, spacing,
-    W2, H2), the mesh a checked int32 array or tensor."""
-    if x.ndim == 4:
-        if x.shape[3] not in (1, 3):
-            raise ValueError(f"a batch must be BxHxWxC with C in (1, 3), got {tuple(x.shape)}")
-        outs = [_remap_frame(x[b], mesher, mode, border, fill) for b in range(x.shape[0])]
-        if outs:
-            return torch.stack(outs) if _is_tensor(x) else np.stack(outs)
-        _, _, W2, H2 = mesher(x.shape[2], x.shape[1])
-        shape = (0, H2, W2, x.shape[3])
-        return x.new_empty(shape) if _is_tensor(x) else np.empty(shape, np.uint8)
-    W, H, Cc = _shape(x)
-    mesh, spacing, W2, H2 = mesher(W, H)
-    if _is_tensor(x) and x.is_cuda:
-        if x.dtype != torch.uint8:
-            raise TypeError("image tensor must be uint8")
-        # the kernel takes pitched views: only the pixels of a row must be packed
-        packed = x.stride(1) == Cc and (x.ndim == 2 or x.stride(2) == 1) and x.stride(0) >= W * Cc
-        xc = x if packed else x.contiguous()
-        out = torch.empty((H2, W2) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device)
-            if _is_tensor(mesh):
-                dm = mesh.to(x.device).contiguous()
-            else:
-                dm = torch.from_numpy(mesh).to(x.device, non_blocking=False)
-            C.remap_device(xc.data_ptr(), xc.stride(0), W, H, Cc, out.data_ptr(), W2 * Cc, dm.data_ptr(), dm.numel(),
-                           spacing, W2, H2, mode, border, fill, stream.cuda_stream)
-        # keep the input and the mesh alive until the stream has consumed them
-        xc.record_stream(stream)
-        dm.record_stream(stream)
-        return out
-    was_tensor = _is_tensor(x)
-    arr = x.numpy() if was_tensor else np.asarray(x)
-    if arr.dtype != np.uint8:
-        raise TypeError("image must be uint8")
-    hm = mesh.cpu().numpy() if _is_tensor(mesh) else mesh
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = C.cpu_remap(np.ascontiguousarray(arr[:, :, 0] if keep else arr), hm, spacing, W2, H2, mode, border, fill)
-    if keep:
-        out = out[:, :, None]
-    return torch.from_numpy(out) if was_tensor else out
+    """One frame (or a batch, frame by frame) through k_remap / cpu_remap; mesher(W, H) -> (W2, H2, (mesh,
+    spacing)), the mesh a checked int32 array or tensor."""
+    def on_device(view, W2, H2, args, stream):
+        mesh, spacing = args
+        if _is_tensor(mesh):
+            dm = mesh.to(stream.device).contiguous()
+        else:
+            dm = torch.from_numpy(mesh).to(stream.device, non_blocking=False)
+        C.remap_device(*view, dm.data_ptr(), dm.numel(), spacing, W2, H2, mode, border, fill, stream.cuda_stream)
+        return (dm,)
+
+    def on_host(arr, W2, H2, args):
+        mesh, spacing = args
+        hm = mesh.cpu().numpy() if _is_tensor(mesh) else mesh
+        return C.cpu_remap(arr, hm, spacing, W2, H2, mode, border, fill)
+    return _frame_stage(x, mesher, on_device, on_host)
 
 
 def _builder(fn, *args):
@@ -839,8 +784,7 @@ def _perspective_mesher(Hm, size, inverse):
 
     def mesher(W, H):
         W2, H2 = _dest_size(size, W, H)
-        mesh, s = _builder(C.perspective_mesh, vals, bool(inverse), W, H, W2, H2, 0)
-        return mesh, s, W2, H2
+        return W2, H2, _builder(C.perspective_mesh, vals, bool(inverse), W, H, W2, H2, 0)
     return mesher
 
 
@@ -859,7 +803,7 @@ def mesh_warp(x, mesh, spacing: int, size=None, mode: str = "bilinear", border: 
         W2, H2 = _dest_size(size, W, H)
         if (W2, H2) not in checked:
             checked[(W2, H2)] = _check_mesh(mesh, spacing, W2, H2)
-        return checked[(W2, H2)], spacing, W2, H2
+        return W2, H2, (checked[(W2, H2)], spacing)
     return _remap_frame(x, mesher, mode, border, fill)
 
 
@@ -914,8 +858,7 @@ def undistort(x, k1: float, k2: float = 0.0, f=None, center=None, mode: str = "b
     cc = None if center is None else [float(v) for v in center]
 
     def mesher(W, H):
-        mesh, s = _builder(C.radial_mesh, float(k1), float(k2), ff, cc, W, H, 0)
-        return mesh, s, W, H
+        return W, H, _builder(C.radial_mesh, float(k1), float(k2), ff, cc, W, H, 0)
     return _remap_frame(x, mesher, mode, border, fill)
 
 
@@ -960,7 +903,7 @@ def remap(x, map_x, map_y, mode: str = "bilinear", border: str = "constant", fil
     H2, W2 = mesh.shape[0] - 1, mesh.shape[1] - 1
     if not (1 <= W2 <= 65535 and 1 <= H2 <= 65535):
         raise ValueError(f"remap: destination size {W2}x{H2} outside 1..65535")
-    return _remap_frame(x, lambda W, H: (mesh, 1, W2, H2), mode, border, fill)
+    return _remap_frame(x, lambda W, H: (W2, H2, (mesh, 1)), mode, border, fill)
 
 
 def remap_reference(x, mesh, spacing: int, size=None, mode: str = "bilinear", border: str = "constant",
@@ -968,15 +911,13 @@ def remap_reference(x, mesh, spacing: int, size=None, mode: str = "bilinear", bo
     """Golden CPU result of `mesh_warp`: the rule as a plain per-pixel loop."""
     mode, border, fill = _warp_args(mode, border, fill)
     spacing = _check_spacing(spacing)
-    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-    W, H, _ = _shape(arr)
-    W2, H2 = _dest_size(size, W, H)
-    hm = _check_mesh(mesh.cpu() if _is_tensor(mesh) else mesh, spacing, W2, H2)
-    hm = hm.numpy() if _is_tensor(hm) else hm
-    keep = arr.ndim == 3 and arr.shape[2] == 1
-    out = _builder(C.golden_remap, np.ascontiguousarray(arr[:, :, 0] if keep else arr), hm, spacing, W2, H2, mode,
-                   border, fill)
-    return out[:, :, None] if keep else out
+
+    def golden(W, H):
+        W2, H2 = _dest_size(size, W, H)
+        hm = _check_mesh(mesh.cpu() if _is_tensor(mesh) else mesh, spacing, W2, H2)
+        hm = hm.numpy() if _is_tensor(hm) else hm
+        return lambda arr: _builder(C.golden_remap, arr, hm, spacing, W2, H2, mode, border, fill)
+    return _reference_frame(x, golden)
 
 
 # ---- connected components (csrc/include/stripe/components.h): labels, stats, area filter ----
