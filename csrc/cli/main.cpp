@@ -28,6 +28,8 @@
 //                [--output mask.pgm] [--stats stats.json] [--backend host|device]
 //   stripe distance --input in.pgm [--chain C] [--to background|foreground] [--backend host|device] --output d.pgm
 //                   [--erode R | --dilate R | --open R | --close R]
+//   stripe binarize --input in.pgm [--chain C] --window K [--method mean|niblack|sauvola|box|std] [--k 0.2] [--c 0]
+//                   [--border B] [--backend host|device] --output mask.pgm
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -767,6 +769,78 @@ int cmd_distance(const Args& a) {
   return 0;
 }
 
+// stripe binarize: the optional chain on one device or on the host, then a window operation of stripe/integral.h on
+// its 1-channel result: the mask of a local threshold (mean, niblack, sauvola), or with --method box / std that
+// plane, to --output; the number of 255 pixels (masks) or the plane's maximum on stdout.
+int cmd_binarize(const Args& a) {
+  STRIPE_CHECK(a.has("input"), "binarize needs --input");
+  STRIPE_CHECK(a.has("window"), "binarize needs --window K (odd)");
+  const bool host_run = a.get("backend", device_count() > 0 ? "device" : "host") == "host";
+  STRIPE_CHECK(host_run || a.get("backend", "device") == "device" || a.get("backend") == "local",
+               "binarize: --backend is host or device, got '" << a.get("backend") << "'");
+  WindowSpec spec;
+  spec.op = parse_window_op(a.get("method", "mean"));
+  spec.K = a.geti("window", 0);
+  spec.C = a.geti("c", 0);
+  const bool has_k = spec.op == WindowOp::Niblack || spec.op == WindowOp::Sauvola;
+  STRIPE_CHECK(has_k || !a.has("k"), "binarize: --method " << window_op_name(spec.op) << " takes no --k");
+  if (has_k) {
+    const std::string ks = a.get("k", "0.2");
+    try {
+      size_t used = 0;
+      const double k = std::stod(ks, &used);
+      STRIPE_CHECK(used == ks.size(), "trailing characters");
+      spec.kq = window_kq(k);
+    } catch (const Error&) {
+      throw;
+    } catch (const std::exception&) {
+      fail("binarize: --k needs a number, got '" + ks + "'");
+    }
+  }
+  const Border border = a.has("border") ? parse_border(a.get("border")) : Border::Reflect101;
+  check_window((int)spec.op, spec.K, border, spec.C, spec.kq);
+  const std::vector<int> devs = parse_int_list(a.get("devices"));
+  const int device = devs.empty() ? 0 : devs[0];
+  Image img = read_image(a.get("input"));
+  if (a.has("chain")) {
+    EngineConfig cfg;
+    cfg.W = img.W, cfg.H = img.H, cfg.C = img.C;
+    cfg.chain = a.get("chain");
+    cfg.border = border;
+    cfg.backend = host_run ? BackendKind::Host : BackendKind::Device;
+    Group g = make_group(host_run ? "host" : "local", 1, devs);
+    PhaseTimes pt;
+    img = run_group(cfg, g.comms, g.devices, img, 1, &pt, nullptr);
+  }
+  check_integral(img.W, img.H, img.C);
+  const int W = img.W, H = img.H;
+  Image out(W, H, 1, NoInit{});
+  if (host_run) {
+    cpu_window(img.data.data(), W, W, H, spec, border, out.data.data(), W, cpu_threads());
+  } else {
+    HIP_CHECK(hipSetDevice(device));
+    uint8_t *ds = nullptr, *dd = nullptr;
+    try {
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), img.bytes()));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dd), img.bytes()));
+      HIP_CHECK(hipMemcpy(ds, img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+      window_device(ds, W, W, H, (int)spec.op, spec.K, (int)border, spec.C, spec.kq, dd, W, nullptr);
+      HIP_CHECK(hipMemcpy(out.data.data(), dd, out.bytes(), hipMemcpyDeviceToHost));
+    } catch (...) {
+      (void)hipFree(ds), (void)hipFree(dd);
+      throw;
+    }
+    HIP_CHECK(hipFree(ds));
+    HIP_CHECK(hipFree(dd));
+  }
+  if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
+  const bool plane = spec.op == WindowOp::Box || spec.op == WindowOp::Std;
+  int64_t n = 0;
+  for (uint8_t v : out.data) n = plane ? std::max<int64_t>(n, v) : n + (v == 255);
+  std::printf("%lld\n", (long long)n);
+  return 0;
+}
+
 int cmd_info(const Args& a) {
   const int n = device_count();
   if (a.get("format") == "json") {
@@ -1079,7 +1153,7 @@ int cmd_bench(const Args& a) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: stripe <run|bench|cmp|gen|convert|info|label|distance> [options]\n"
+               "usage: stripe <run|bench|cmp|gen|convert|info|label|distance|binarize> [options]\n"
                "  run   --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95]\n"
                "        [--chain C | --preset ref-gpu|ref-cpu] [--ranks N]\n"
                "        [--backend rccl|local|host] [--devices 0,1,..] [--border MODE] [--no-halo]\n"
@@ -1117,7 +1191,12 @@ void usage() {
                "  distance --input in.pgm [--chain C] [--to background|foreground] [--backend host|device] --output d.pgm\n"
                "        [--erode R | --dilate R | --open R | --close R]\n"
                "            (exact Euclidean distance transform of the chain's 1-channel result: min(255, floor(d)) as a PGM,\n"
-               "             or the mask of the disc operation of radius R; the largest finite d^2 or 'none' on stdout)\n");
+               "             or the mask of the disc operation of radius R; the largest finite d^2 or 'none' on stdout)\n"
+               "  binarize --input in.pgm [--chain C] --window K [--method mean|niblack|sauvola|box|std] [--k 0.2] [--c 0]\n"
+               "        [--border B] [--backend host|device] --output mask.pgm\n"
+               "            (local threshold of the chain's 1-channel result over a K x K window, any odd K up to 4095\n"
+               "             (255 for niblack, sauvola, std) on an integral image; box / std write that plane;\n"
+               "             the number of 255 pixels, or the plane's maximum, on stdout)\n");
 }
 
 }  // namespace
@@ -1133,6 +1212,7 @@ int main(int argc, char** argv) {
     if (a.cmd == "info") return cmd_info(a);
     if (a.cmd == "label") return cmd_label(a);
     if (a.cmd == "distance") return cmd_distance(a);
+    if (a.cmd == "binarize") return cmd_binarize(a);
     usage();
     return a.cmd.empty() || a.cmd == "help" || a.cmd == "--help" ? 0 : 2;
   } catch (const std::exception& e) {

@@ -13,6 +13,7 @@
 
 #include "stripe/components.h"
 #include "stripe/distance.h"
+#include "stripe/integral.h"
 #include "stripe/orient.h"
 #include "stripe/rank_net.h"
 #include "stripe/remap.h"
@@ -1233,6 +1234,105 @@ Image cpu_disk_morph(const Image& img, DiskOp op, double radius, int threads) {
     case DiskOp::Close: return cpu_distance_mask(cpu_distance_mask(img, true, t, false, threads), false, t, true, threads);
   }
   fail("distance: unknown disc operation");
+}
+
+// ---- integral images (stripe/integral.h) ----
+namespace {
+
+// The wrapping u32 integral of a frame of We x He values given row by row: t is (He + 1) rows of pitch tp, row 0
+// and column 0 zero.  Row blocks are scanned on their own (a running row sum plus the row above inside the
+// block), then every block but the first takes the carry row: the last row of the block above, itself carried.
+// u32 addition is associative modulo 2^32, so the table does not depend on the number of blocks.
+template <class RowFn>
+void sat_build(int We, int He, uint32_t* t, int64_t tp, int threads, RowFn&& row) {
+  const int T = std::max(1, std::min(threads, He));
+  std::fill(t, t + We + 1, 0u);
+  const auto ya = [&](int b) { return (int)((int64_t)He * b / T); };
+  run_blocks(T, [&](int b) {
+    std::vector<uint32_t> v((size_t)We);
+    for (int y = ya(b); y < ya(b + 1); ++y) {
+      row(y, v.data());
+      uint32_t* o = t + (int64_t)(y + 1) * tp;
+      const uint32_t* up = o - tp;
+      const bool first = y == ya(b);
+      uint32_t run = 0;
+      o[0] = 0;
+      for (int x = 0; x < We; ++x) {
+        run += v[(size_t)x];
+        o[x + 1] = run + (first ? 0u : up[x + 1]);
+      }
+    }
+  });
+  if (T == 1) return;
+  // block b's carry is the finished last row of block b - 1: finish those rows in order, then the rest at once
+  for (int b = 1; b < T; ++b) {
+    const uint32_t* c = t + (int64_t)ya(b) * tp;
+    uint32_t* last = t + (int64_t)ya(b + 1) * tp;
+    if (ya(b + 1) > ya(b))
+      for (int x = 1; x <= We; ++x) last[x] += c[x];
+  }
+  run_blocks(T, [&](int b) {
+    if (b == 0) return;
+    const uint32_t* c = t + (int64_t)ya(b) * tp;
+    for (int y = ya(b); y + 1 < ya(b + 1); ++y) {
+      uint32_t* o = t + (int64_t)(y + 1) * tp;
+      for (int x = 1; x <= We; ++x) o[x] += c[x];
+    }
+  });
+}
+
+}  // namespace
+
+void cpu_integral(const uint8_t* src, int64_t sp, int W, int H, bool squared, int32_t* out, int64_t op, int threads) {
+  check_integral(W, H, 1);
+  STRIPE_CHECK(src && out, "integral: empty image");
+  STRIPE_CHECK(sp >= W && op >= (int64_t)W + 1, "integral: pitch smaller than a row");
+  sat_build(W, H, reinterpret_cast<uint32_t*>(out), op, threads, [&](int y, uint32_t* v) {
+    const uint8_t* r = src + (int64_t)y * sp;
+    for (int x = 0; x < W; ++x) v[x] = squared ? (uint32_t)r[x] * r[x] : (uint32_t)r[x];
+  });
+}
+
+void cpu_window(const uint8_t* src, int64_t sp, int W, int H, const WindowSpec& spec, Border border, uint8_t* dst,
+                int64_t dp, int threads) {
+  check_integral(W, H, 1);
+  check_window((int)spec.op, spec.K, border, spec.C, spec.kq);
+  STRIPE_CHECK(src && dst, "integral: empty image");
+  STRIPE_CHECK(sp >= W && dp >= W, "integral: pitch smaller than a row");
+  const int K = spec.K, R = K / 2, We = W + 2 * R, He = H + 2 * R;
+  const int64_t tp = (int64_t)We + 1;
+  const bool sq = window_uses_squares(spec.op);
+  std::vector<int> cx((size_t)We);
+  for (int x = 0; x < We; ++x) cx[(size_t)x] = border_index(x - R, W, border);
+  const auto ext_row = [&](int y, uint32_t* v, bool squared) {
+    const int sy = border_index(y - R, H, border);
+    if (sy < 0) {
+      std::fill(v, v + We, 0u);
+      return;
+    }
+    const uint8_t* r = src + (int64_t)sy * sp;
+    for (int x = 0; x < We; ++x) {
+      const uint32_t p = cx[(size_t)x] < 0 ? 0u : r[cx[(size_t)x]];
+      v[x] = squared ? p * p : p;
+    }
+  };
+  std::vector<uint32_t> ta((size_t)(tp * (He + 1))), tb(sq ? ta.size() : 0);
+  sat_build(We, He, ta.data(), tp, threads, [&](int y, uint32_t* v) { ext_row(y, v, false); });
+  if (sq) sat_build(We, He, tb.data(), tp, threads, [&](int y, uint32_t* v) { ext_row(y, v, true); });
+  const uint32_t N = (uint32_t)K * (uint32_t)K;
+  parallel_rows(0, H, 24 * (int64_t)W, std::max(1, threads), [&](int y0, int y1) {
+    for (int y = y0; y < y1; ++y) {
+      const uint32_t *a0 = ta.data() + (int64_t)y * tp, *a1 = a0 + (int64_t)K * tp;
+      const uint32_t *b0 = sq ? tb.data() + (int64_t)y * tp : nullptr, *b1 = sq ? b0 + (int64_t)K * tp : nullptr;
+      const uint8_t* r = src + (int64_t)y * sp;
+      uint8_t* o = dst + (int64_t)y * dp;
+      for (int x = 0; x < W; ++x) {
+        const uint32_t A = a1[x + K] - a0[x + K] - a1[x] + a0[x];
+        const uint32_t B = sq ? b1[x + K] - b0[x + K] - b1[x] + b0[x] : 0u;
+        o[x] = window_rule((int)spec.op, r[x], A, B, N, spec.C, spec.kq);
+      }
+    }
+  });
 }
 
 }  // namespace stripe

@@ -264,6 +264,29 @@ void launch_disk_morph(const DistanceLaunch& L, int op, hipStream_t s) {
   launch_disk_morph_kernels(L, op, s);
 }
 
+void launch_integral(const IntegralLaunch& L, hipStream_t s) {
+  // host-side shape checks before any kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad integral launch: null src or dst");
+  check_integral(L.W, L.H, 1);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "integral: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W + 1,
+               "integral: dst_pitch " << L.dst_pitch << " < the row's " << L.W + 1 << " elements");
+  STRIPE_CHECK((reinterpret_cast<uintptr_t>(L.dst) & 3) == 0, "integral: the int32 plane must be aligned to 4 bytes");
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_integral_kernels(L, s);
+}
+
+void launch_window(const WindowLaunch& L, hipStream_t s) {
+  STRIPE_CHECK(L.src && L.dst, "bad window launch: null src or dst");
+  check_integral(L.W, L.H, 1);
+  STRIPE_CHECK(L.border >= 0 && L.border <= (int)Border::Skip, "integral: unknown border " << L.border);
+  check_window(L.op, L.K, (Border)L.border, L.C, L.kq);
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "integral: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W, "integral: dst_pitch " << L.dst_pitch << " < row bytes " << L.W);
+  (void)hipGetLastError();
+  launch_window_kernels(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

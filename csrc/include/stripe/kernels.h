@@ -13,6 +13,7 @@
 #include "stripe/components.h"
 #include "stripe/distance.h"
 #include "stripe/image.h"
+#include "stripe/integral.h"
 #include "stripe/orient.h"
 #include "stripe/remap.h"
 #include "stripe/resize.h"
@@ -421,6 +422,55 @@ void distance_device(const uint8_t* src, int64_t src_pitch, int W, int H, bool t
 void disk_morph_device(const uint8_t* src, int64_t src_pitch, int W, int H, int op, int64_t t, uint8_t* dst,
                        int64_t dst_pitch, hipStream_t s);
 void distance_release_scratch();  // frees the cached scratch of every device (waits for the devices)
+
+// Integral images and the window operations on them (csrc/hip/integral.hip
+// k_sat_*; the rule: stripe/integral.h).  Addressing as k_orient: 64-bit on
+// pitched views, the source pitch any value >= W at any alignment, no byte
+// outside a source row's W bytes read, nothing outside a destination row's
+// elements written (W + 1 int32 per row of the integral, whose pitch counts
+// elements and whose plane is aligned to 4 bytes; W bytes of a window result).
+//
+// Reduce, carry, scan over wave tiles of kSatTile x kSatTile pixels of the
+// extended frame, kSatWaves tiles side by side per workgroup: k_sat_reduce
+// writes column, row and tile totals, k_sat_carry prefix-sums them,
+// k_sat_scan writes the wrapping u32 table with a DPP wave scan per row; no
+// kernel uses LDS (sat_lds_bytes).  k_sat_window reads four corners per table
+// and stores kSatWindowPixels bytes per lane.  No host synchronisation; the
+// aggregates and the window operations' tables are cached per device, stream,
+// extended size and number of tables until integral_release_scratch.
+constexpr int kSatTile = 64;          // rows and columns of a wave's tile
+constexpr int kSatWaves = 4;          // wave tiles side by side in a workgroup
+constexpr int kSatWindowPixels = 4;   // pixels per lane of k_sat_window
+constexpr int sat_lds_bytes() { return 0; }
+struct IntegralLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;  // bytes
+  int W = 0, H = 0;
+  bool squared = false;
+  int32_t* dst = nullptr;  // (H + 1) x (W + 1)
+  int64_t dst_pitch = 0;   // elements
+};
+struct WindowLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;
+  int W = 0, H = 0;
+  int op = 0;  // WindowOp
+  int K = 1;
+  int border = 0;  // Border
+  int C = 0;
+  int64_t kq = 0;
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+};
+void launch_integral(const IntegralLaunch& L, hipStream_t s);          // dispatch.cpp: checks, then the kernels
+void launch_integral_kernels(const IntegralLaunch& L, hipStream_t s);  // integral.hip
+void launch_window(const WindowLaunch& L, hipStream_t s);              // dispatch.cpp
+void launch_window_kernels(const WindowLaunch& L, hipStream_t s);      // integral.hip
+void integral_device(const uint8_t* src, int64_t src_pitch, int W, int H, bool squared, int32_t* dst, int64_t dst_pitch,
+                     hipStream_t s);
+void window_device(const uint8_t* src, int64_t src_pitch, int W, int H, int op, int K, int border, int C, int64_t kq,
+                   uint8_t* dst, int64_t dst_pitch, hipStream_t s);
+void integral_release_scratch();  // frees the cached scratch of every device (waits for the devices)
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

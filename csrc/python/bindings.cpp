@@ -1018,6 +1018,108 @@ PYBIND11_MODULE(_C, m) {
   m.attr("DISTANCE_MAX_SIDE") = kDistanceMaxSide;
   m.attr("DISTANCE_MODES") = std::vector<std::string>{"squared", "u8", "mask_above", "mask_within"};
 
+  // ---- integral images and the window operations (stripe/integral.h); entry points of their own ----
+  static const auto table_to_numpy = [](const std::vector<int32_t>& t, int W, int H) {
+    py::array_t<int32_t> a(std::vector<py::ssize_t>{H + 1, W + 1});
+    std::memcpy(a.mutable_data(), t.data(), t.size() * sizeof(int32_t));
+    return a;
+  };
+  static const auto window_spec = [](const std::string& op, int K, int c, double k) {
+    WindowSpec spec;
+    spec.op = parse_window_op(op);
+    spec.K = K, spec.C = c;
+    spec.kq = window_kq(k);
+    return spec;
+  };
+  m.def("golden_integral", [table = table_to_numpy](const U8Array& a, bool squared) {
+    const Image img = image_from_numpy(a);
+    std::vector<int32_t> t;
+    {
+      py::gil_scoped_release nogil;
+      golden_integral(img, squared, &t);
+    }
+    return table(t, img.W, img.H);
+  }, py::arg("image"), py::arg("squared") = false,
+     "int32 (H + 1) x (W + 1): I[y][x] = the sum of p (p^2) over y' < y, x' < x modulo 2^32, cv::integral's layout");
+  m.def("cpu_integral", [table = table_to_numpy](const U8Array& a, bool squared, int threads) {
+    const Image img = image_from_numpy(a);
+    check_integral(img.W, img.H, img.C);
+    std::vector<int32_t> t(((size_t)img.W + 1) * ((size_t)img.H + 1));
+    {
+      py::gil_scoped_release nogil;
+      cpu_integral(img.data.data(), img.W, img.W, img.H, squared, t.data(), img.W + 1,
+                   threads > 0 ? threads : cpu_threads());
+    }
+    return table(t, img.W, img.H);
+  }, py::arg("image"), py::arg("squared") = false, py::arg("threads") = 0,
+     "the integral on the host executor (block-local scans over row blocks plus carries)");
+  m.def("golden_window", [spec_of = window_spec](const U8Array& a, const std::string& op, int K, const std::string& border,
+                                                 int c, double k) {
+    const Image img = image_from_numpy(a);
+    const WindowSpec spec = spec_of(op, K, c, k);
+    const Border b = parse_border(border);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_window(img, spec, b);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("ksize"), py::arg("border") = "reflect101", py::arg("c") = 0,
+     py::arg("k") = 0.0, "box / std / mean / niblack / sauvola over a K x K window: the plain loop over the extended frame");
+  m.def("cpu_window", [spec_of = window_spec](const U8Array& a, const std::string& op, int K, const std::string& border,
+                                              int c, double k, int threads) {
+    const Image img = image_from_numpy(a);
+    check_integral(img.W, img.H, img.C);
+    const WindowSpec spec = spec_of(op, K, c, k);
+    const Border b = parse_border(border);
+    Image out(img.W, img.H, 1);
+    {
+      py::gil_scoped_release nogil;
+      cpu_window(img.data.data(), img.W, img.W, img.H, spec, b, out.data.data(), img.W,
+                 threads > 0 ? threads : cpu_threads());
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("op"), py::arg("ksize"), py::arg("border") = "reflect101", py::arg("c") = 0,
+     py::arg("k") = 0.0, py::arg("threads") = 0,
+     "the window operations on the host executor: the wrapping u32 tables, then four corners per table and pixel");
+  m.def("window_kq", [](double k) { return window_kq(k); }, py::arg("k"),
+        "nearbyint(4096 k), ties to even; refuses a non-finite k and |k| > 4");
+  m.def("integral_device", [](uintptr_t src, int64_t src_pitch, int W, int H, bool squared, uintptr_t dst,
+                              int64_t dst_pitch, uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    integral_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, squared, reinterpret_cast<int32_t*>(dst),
+                    dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("squared"), py::arg("dst"),
+     py::arg("dst_pitch"), py::arg("stream") = 0,
+     "k_sat_* on a pitched u8 device frame (any alignment) into an int32 plane of (H + 1) x (W + 1) (pitch in "
+     "elements); queued on the stream, no synchronisation");
+  m.def("window_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int op, int K, const std::string& border,
+                            int c, int64_t kq, uintptr_t dst, int64_t dst_pitch, uintptr_t stream) {
+    const int b = (int)parse_border(border);
+    py::gil_scoped_release nogil;
+    window_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, op, K, b, c, kq,
+                  reinterpret_cast<uint8_t*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("op"), py::arg("ksize"),
+     py::arg("border"), py::arg("c"), py::arg("kq"), py::arg("dst"), py::arg("dst_pitch"), py::arg("stream") = 0,
+     "the tables of the extended frame (k_sat_reduce / carry / scan), then k_sat_window<op> (op: the index in "
+     "WINDOW_OPS, kq = window_kq(k)); queued on the stream, no synchronisation");
+  m.def("integral_release_scratch", [] {
+    py::gil_scoped_release nogil;
+    integral_release_scratch();
+  }, "free the cached device scratch of the integral images");
+  m.def("integral_tile", [] { return py::make_tuple(kSatTile, kSatWaves, kSatWindowPixels); },
+        "(rows and columns of a wave's tile, wave tiles side by side in a workgroup, pixels per lane of k_sat_window)");
+  m.def("integral_lds", [] {
+    py::dict d;
+    for (const char* name : {"k_sat_reduce", "k_sat_carry", "k_sat_scan", "k_sat_window"}) d[name] = sat_lds_bytes();
+    return d;
+  }, "LDS bytes of each k_sat_* kernel");
+  m.attr("INTEGRAL_MAX_SIDE") = kIntegralMaxSide;
+  m.attr("WINDOW_MAX_K") = kWindowMaxK;
+  m.attr("WINDOW_MAX_K_SQUARES") = kWindowMaxKSquares;
+  m.attr("WINDOW_MAX_ABS_K") = kWindowMaxAbsK;
+  m.attr("WINDOW_OPS") = std::vector<std::string>{"box", "std", "mean", "niblack", "sauvola"};
+
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
         py::arg("image"), "int64 counts of shape (C, 256)");

@@ -335,7 +335,8 @@ def black_hat(x, k: int = 3, border: str = "reflect101"):
 
 
 def adaptive_threshold(x, ksize: int = 3, c: int = 0, border: str = "reflect101"):
-    """x > box_ksize(x) - c ? 255 : 0 (OpenCV's ADAPTIVE_THRESH_MEAN_C on box's own rounding)."""
+    """x > box_ksize(x) - c ? 255 : 0 (OpenCV's ADAPTIVE_THRESH_MEAN_C on box's own rounding); ksize 3 or 5, for
+    larger windows see `local_threshold`."""
     return apply(x, f"threshold:adaptive:{int(ksize)}:{int(c)}", border)
 
 
@@ -1217,10 +1218,142 @@ def close_disk(x, radius):
     return _disk_morph(x, "close", radius)
 
 
+# ---- integral images: any-size box filter and local thresholds (csrc/include/stripe/integral.h) ----
+WINDOW_OPS = tuple(C.WINDOW_OPS)
+WINDOW_MAX_K = int(C.WINDOW_MAX_K)
+WINDOW_MAX_K_SQUARES = int(C.WINDOW_MAX_K_SQUARES)
+LOCAL_THRESHOLD_METHODS = ("mean", "niblack", "sauvola")
+_WINDOW_OP = {name: k for k, name in enumerate(C.WINDOW_OPS)}
+_WINDOW_BORDERS = ("reflect101", "replicate", "constant")
+
+
+def _integral_shape(x):
+    """(W, H) of one 1-channel frame HxW or HxWx1 within the side limit; everything else is refused."""
+    if x.ndim == 4:
+        raise ValueError(f"integral: one frame at a time, got a batch of shape {tuple(x.shape)}")
+    if x.ndim == 3 and x.shape[2] == 3:
+        raise ValueError("integral: needs a 1-channel image, got C = 3; convert first (gray, threshold, ...)")
+    if not (x.ndim == 2 or (x.ndim == 3 and x.shape[2] == 1)):
+        raise ValueError(f"integral: the image must be HxW or HxWx1 uint8, got shape {tuple(x.shape)}")
+    W, H = int(x.shape[1]), int(x.shape[0])
+    if W < 1 or H < 1:
+        raise ValueError(f"integral: empty image ({W}x{H})")
+    if W > C.INTEGRAL_MAX_SIDE or H > C.INTEGRAL_MAX_SIDE:
+        raise ValueError(f"integral: {W}x{H} has a side above {C.INTEGRAL_MAX_SIDE}")
+    return W, H
+
+
+def integral(x, squared: bool = False):
+    """The integral image (summed-area table) of a 1-channel frame, OpenCV's layout.
+
+    x: HxW or HxWx1 uint8, sides up to 32767.  The result is (H + 1) x (W + 1) int32 with row 0 and column 0
+    zero and I[y][x] the sum of p (of p^2 with squared=True) over y' < y, x' < x, modulo 2^32 like
+    cv::integral CV_32S: a rectangle sum below 2^32 is still exact as I[d] - I[b] - I[c] + I[a] in wrapping
+    arithmetic.  A CUDA tensor runs on the k_sat_* HIP kernels on torch's current stream without any
+    synchronisation and gives a CUDA tensor; numpy arrays / CPU tensors run on the threaded host executor and
+    keep their container.  Bit-identical to `integral_reference`."""
+    W, H = _integral_shape(x)
+    if _is_tensor(x) and x.is_cuda:
+        xc = _device_mask(x, W)
+        out = torch.empty((H + 1, W + 1), dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            _builder(C.integral_device, xc.data_ptr(), xc.stride(0) if H > 1 else W, W, H, bool(squared),
+                     out.data_ptr(), W + 1, stream.cuda_stream)
+        # keep the input alive until the stream has consumed it
+        xc.record_stream(stream)
+        return out
+    out = _builder(C.cpu_integral, _host_mask(x), bool(squared))
+    return torch.from_numpy(out) if _is_tensor(x) else out
+
+
+def integral_reference(x, squared: bool = False):
+    """Golden CPU result of `integral` (numpy): the plain double loop."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _integral_shape(arr)
+    return _builder(C.golden_integral, _host_mask(arr), bool(squared))
+
+
+def _window_args(op, ksize, border, c, k):
+    """(op, K, border, c, k) checked the way every layer words it; k is None for the operations without one."""
+    if op not in _WINDOW_OP:
+        raise ValueError(f"integral: the window operation must be one of {', '.join(WINDOW_OPS)}, got {op!r}")
+    if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)):
+        raise ValueError(f"integral: the window must be an odd integer, got {ksize!r}")
+    if border not in _WINDOW_BORDERS:
+        raise ValueError(f"integral: the border must be reflect101, replicate or constant, got {border!r}")
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+        raise ValueError(f"integral: c must be an integer, got {c!r}")
+    if op == "sauvola" and int(c) != 0:
+        raise ValueError("integral: sauvola takes no c (its threshold scales the mean); use niblack for an offset")
+    if op in ("niblack", "sauvola"):
+        k = 0.2 if k is None else float(k)
+    elif k is not None:
+        raise ValueError(f"integral: {op} takes no k, got {k!r}")
+    else:
+        k = 0.0
+    return op, int(ksize), border, int(c), k
+
+
+def _check_one_channel(x):
+    if (x.ndim == 3 and x.shape[2] == 3) or (x.ndim == 4 and x.shape[3] == 3):
+        raise ValueError("integral: needs a 1-channel image, got C = 3; convert first (gray, threshold, ...)")
+
+
+def _window_stage(x, op, ksize, border, c=0, k=None):
+    op, K, border, c, k = _window_args(op, ksize, border, c, k)
+    _check_one_channel(x)
+    kq = int(_builder(C.window_kq, k))
+
+    def on_device(view, W2, H2, _, stream):
+        src, sp, W, H, _c, dst, dp = view
+        _builder(C.window_device, src, sp, W, H, _WINDOW_OP[op], K, border, c, kq, dst, dp, stream.cuda_stream)
+
+    return _frame_stage(x, lambda W, H: (W, H, None), on_device,
+                        lambda arr, W2, H2, _: _builder(C.cpu_window, arr, op, K, border, c, k))
+
+
+def box_filter(x, ksize: int, border: str = "reflect101"):
+    """The mean over a ksize x ksize window, any odd ksize up to 4095, in a constant number of passes:
+    (A + N/2) / N with A the window sum over the frame extended by the border and N = ksize^2 (box3 / box5's
+    rule, so ksize 3 and 5 equal `box_blur`).  x: HxW, HxWx1 or a Bx..x1 batch, uint8; the result has x's shape
+    and container.  CUDA tensors run on the k_sat_* HIP kernels (integral image, then four table reads per
+    pixel) on torch's current stream; numpy arrays / CPU tensors on the host executor; bit-identical to
+    `window_reference`."""
+    return _window_stage(x, "box", ksize, border)
+
+
+def local_std(x, ksize: int, border: str = "reflect101"):
+    """The local standard deviation over a ksize x ksize window (odd, up to 255): floor(isqrt(N B - A^2) / N)
+    with A and B the window sums of p and p^2, at most 127."""
+    return _window_stage(x, "std", ksize, border)
+
+
+def local_threshold(x, ksize: int, method: str = "mean", c: int = 0, k=None, border: str = "reflect101"):
+    """A 0 / 255 mask from a threshold that follows the local window (document binarisation).
+
+    method="mean": p > m - c with m the box mean (`adaptive_threshold`'s rule at any odd ksize up to 4095);
+    "niblack": p > m + k s - c; "sauvola": p > m (1 + k (s / 128 - 1)), with s the local standard deviation,
+    ksize up to 255, k (default 0.2, |k| <= 4) quantised to 1/4096; both in exact integers (the rule:
+    stripe/integral.h).  c is an integer in -255..255 and is refused for sauvola."""
+    if method not in LOCAL_THRESHOLD_METHODS:
+        raise ValueError(f"integral: method must be one of {', '.join(LOCAL_THRESHOLD_METHODS)}, got {method!r}")
+    return _window_stage(x, method, ksize, border, c, k)
+
+
+def window_reference(x, op: str, ksize: int, border: str = "reflect101", c: int = 0, k=None):
+    """Golden CPU result of `box_filter` ("box"), `local_std` ("std") and `local_threshold` ("mean", "niblack",
+    "sauvola"): the plain loop over the extended frame (numpy)."""
+    op, K, border, c, k = _window_args(op, ksize, border, c, k)
+    _check_one_channel(x)
+    return _reference_frame(x, lambda W, H: lambda arr: _builder(C.golden_window, arr, op, K, border, c, k))
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
     C.distance_release_scratch()
+    C.integral_release_scratch()
 
 
 __all__ = [
@@ -1240,4 +1373,6 @@ __all__ = [
     "STAT_COLUMNS",
     "distance_transform", "distance_transform_reference", "erode_disk", "dilate_disk", "open_disk", "close_disk",
     "DISTANCE_NONE", "DISTANCE_OUTPUTS",
+    "integral", "integral_reference", "box_filter", "local_std", "local_threshold", "window_reference",
+    "WINDOW_OPS", "WINDOW_MAX_K", "WINDOW_MAX_K_SQUARES", "LOCAL_THRESHOLD_METHODS",
 ]

@@ -54,6 +54,7 @@ CORE_SOURCES = [
     "core/remap.cpp",
     "core/components.cpp",
     "core/distance.cpp",
+    "core/integral.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -73,6 +74,7 @@ CORE_SOURCES = [
     "hip/remap.hip",
     "hip/components.hip",
     "hip/distance.hip",
+    "hip/integral.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
