@@ -30,6 +30,8 @@
 //                   [--erode R | --dilate R | --open R | --close R]
 //   stripe binarize --input in.pgm [--chain C] --window K [--method mean|niblack|sauvola|box|std] [--k 0.2] [--c 0]
 //                   [--border B] [--backend host|device] --output mask.pgm
+//   stripe edges --input in.pgm [--chain C] --low L --high H [--norm l1|l2] [--border B] [--backend host|device]
+//                --output edges.pgm
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -841,6 +843,60 @@ int cmd_binarize(const Args& a) {
   return 0;
 }
 
+// stripe edges: the optional chain on one device or on the host, then Canny edge detection (stripe/canny.h) of its
+// 1-channel result: the 255 / 0 edge map to --output; the number of edge pixels on stdout.
+int cmd_edges(const Args& a) {
+  STRIPE_CHECK(a.has("input"), "edges needs --input");
+  STRIPE_CHECK(a.has("low") && a.has("high"), "edges needs --low and --high");
+  const bool host_run = a.get("backend", device_count() > 0 ? "device" : "host") == "host";
+  STRIPE_CHECK(host_run || a.get("backend", "device") == "device" || a.get("backend") == "local",
+               "edges: --backend is host or device, got '" << a.get("backend") << "'");
+  const auto threshold = [&a](const char* name) {
+    const std::string v = a.get(name);
+    try {
+      size_t used = 0;
+      const long long t = std::stoll(v, &used);
+      if (used == v.size()) return (int64_t)t;
+    } catch (const std::exception&) {
+    }
+    fail(std::string("edges: --") + name + " needs an integer, got '" + v + "'");
+  };
+  const int64_t low = threshold("low"), high = threshold("high");
+  check_thresholds(low, high, kCannyMaxThreshold);
+  const CannyNorm norm = parse_canny_norm(a.get("norm", "l1"));
+  const Border border = a.has("border") ? parse_border(a.get("border")) : Border::Reflect101;
+  const std::vector<int> devs = parse_int_list(a.get("devices"));
+  const int device = devs.empty() ? 0 : devs[0];
+  Image img = read_image(a.get("input"));
+  if (a.has("chain")) {
+    EngineConfig cfg;
+    cfg.W = img.W, cfg.H = img.H, cfg.C = img.C;
+    cfg.chain = a.get("chain");
+    cfg.border = border;
+    cfg.backend = host_run ? BackendKind::Host : BackendKind::Device;
+    Group g = make_group(host_run ? "host" : "local", 1, devs);
+    PhaseTimes pt;
+    img = run_group(cfg, g.comms, g.devices, img, 1, &pt, nullptr);
+  }
+  check_canny(img.W, img.H, img.C, low, high, (int)norm, border);
+  const int W = img.W, H = img.H;
+  Image out(W, H, 1, NoInit{});
+  if (host_run) {
+    cpu_canny(img.data.data(), W, W, H, (int)low, (int)high, norm, border, out.data.data(), W, cpu_threads());
+  } else {
+    HIP_CHECK(hipSetDevice(device));
+    Buffer ds(img.bytes(), true), dd(img.bytes(), true);
+    HIP_CHECK(hipMemcpy(ds.data(), img.data.data(), img.bytes(), hipMemcpyHostToDevice));
+    canny_device(ds.data(), W, W, H, (int)low, (int)high, (int)norm, (int)border, dd.data(), W, nullptr);
+    HIP_CHECK(hipMemcpy(out.data.data(), dd.data(), out.bytes(), hipMemcpyDeviceToHost));
+  }
+  if (a.has("output")) write_image(a.get("output"), out, a.geti("quality", 95));
+  int64_t n = 0;
+  for (uint8_t v : out.data) n += v == 255;
+  std::printf("%lld\n", (long long)n);
+  return 0;
+}
+
 int cmd_info(const Args& a) {
   const int n = device_count();
   if (a.get("format") == "json") {
@@ -1153,7 +1209,7 @@ int cmd_bench(const Args& a) {
 
 void usage() {
   std::fprintf(stderr,
-               "usage: stripe <run|bench|cmp|gen|convert|info|label|distance|binarize> [options]\n"
+               "usage: stripe <run|bench|cmp|gen|convert|info|label|distance|binarize|edges> [options]\n"
                "  run   --input in.ppm|in.jpg --output out.ppm|out.jpg [--quality 95]\n"
                "        [--chain C | --preset ref-gpu|ref-cpu] [--ranks N]\n"
                "        [--backend rccl|local|host] [--devices 0,1,..] [--border MODE] [--no-halo]\n"
@@ -1196,7 +1252,13 @@ void usage() {
                "        [--border B] [--backend host|device] --output mask.pgm\n"
                "            (local threshold of the chain's 1-channel result over a K x K window, any odd K up to 4095\n"
                "             (255 for niblack, sauvola, std) on an integral image; box / std write that plane;\n"
-               "             the number of 255 pixels, or the plane's maximum, on stdout)\n");
+               "             the number of 255 pixels, or the plane's maximum, on stdout)\n"
+               "  edges --input in.pgm [--chain C] --low L --high H [--norm l1|l2] [--border B] [--backend host|device]\n"
+               "        --output edges.pgm\n"
+               "            (Canny edges of the chain's 1-channel result: Sobel gradient, non-maximum suppression and\n"
+               "             8-connected hysteresis between the integer thresholds 0 <= L <= H <= 2040, compared with\n"
+               "             |Gx| + |Gy| (l1) or through their squares with Gx^2 + Gy^2 (l2); 255 / 0 as a PGM; the\n"
+               "             number of edge pixels on stdout; blur first with --chain gaussian5)\n");
 }
 
 }  // namespace
@@ -1213,6 +1275,7 @@ int main(int argc, char** argv) {
     if (a.cmd == "label") return cmd_label(a);
     if (a.cmd == "distance") return cmd_distance(a);
     if (a.cmd == "binarize") return cmd_binarize(a);
+    if (a.cmd == "edges") return cmd_edges(a);
     usage();
     return a.cmd.empty() || a.cmd == "help" || a.cmd == "--help" ? 0 : 2;
   } catch (const std::exception& e) {

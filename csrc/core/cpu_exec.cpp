@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "stripe/canny.h"
 #include "stripe/components.h"
 #include "stripe/distance.h"
 #include "stripe/integral.h"
@@ -1333,6 +1334,113 @@ void cpu_window(const uint8_t* src, int64_t sp, int W, int H, const WindowSpec& 
       }
     }
   });
+}
+
+// ---- canny and hysteresis thresholding (stripe/canny.h) ----
+namespace {
+
+// magnitudes carry their sector in the top bits (a magnitude is below 2^21)
+constexpr int kCannySectorShift = 24;
+constexpr uint32_t kCannyMagMask = (1u << kCannySectorShift) - 1u;
+
+}  // namespace
+
+void cpu_canny_classes(const uint8_t* src, int64_t sp, int W, int H, int low, int high, CannyNorm norm, Border border,
+                       uint8_t* dst, int64_t dp, int threads) {
+  check_canny(W, H, 1, low, high, (int)norm, border);
+  STRIPE_CHECK(src && dst, "canny: empty image");
+  STRIPE_CHECK(sp >= W && dp >= W, "canny: pitch smaller than a row");
+  const bool l2 = norm == CannyNorm::L2;
+  const uint32_t lo = l2 ? (uint32_t)low * low : (uint32_t)low, hi = l2 ? (uint32_t)high * high : (uint32_t)high;
+  std::vector<int> cx((size_t)W + 2);
+  for (int x = 0; x < W + 2; ++x) cx[(size_t)x] = border_index(x - 1, W, border);
+  const size_t We = (size_t)W + 2;
+  parallel_rows(0, H, 16 * (int64_t)W, std::max(1, threads), [&](int y0, int y1) {
+    const int n = y1 - y0;
+    // the extended rows y0 - 2 .. y1 + 1 (those of magnitude rows outside the frame stay unused), then the
+    // magnitude rows y0 - 1 .. y1 with a zero column on both sides; rows outside the frame are zero
+    std::vector<uint8_t> P(We * (size_t)(n + 4));
+    std::vector<uint32_t> M(We * (size_t)(n + 2), 0u);
+    for (int r = 0; r < n + 4; ++r) {
+      const int y = y0 - 2 + r;
+      if (y < -1 || y > H) continue;
+      const int sy = border_index(y, H, border);
+      uint8_t* p = P.data() + We * (size_t)r;
+      if (sy < 0) {
+        std::fill(p, p + We, (uint8_t)0);
+        continue;
+      }
+      const uint8_t* s = src + (int64_t)sy * sp;
+      for (size_t x = 0; x < We; ++x) p[x] = cx[x] < 0 ? (uint8_t)0 : s[cx[x]];
+    }
+    for (int r = 0; r < n + 2; ++r) {
+      const int y = y0 - 1 + r;
+      if (y < 0 || y >= H) continue;
+      const uint8_t *a = P.data() + We * (size_t)r, *b = a + We, *c = b + We;  // the extended rows y - 1, y, y + 1
+      uint32_t* m = M.data() + We * (size_t)r + 1;
+      for (int x = 0; x < W; ++x) {
+        const int gx = (a[x + 2] + 2 * b[x + 2] + c[x + 2]) - (a[x] + 2 * b[x] + c[x]);
+        const int gy = (c[x] + 2 * c[x + 1] + c[x + 2]) - (a[x] + 2 * a[x + 1] + a[x + 2]);
+        m[x] = canny_magnitude(gx, gy, l2) | ((uint32_t)canny_sector(gx, gy) << kCannySectorShift);
+      }
+    }
+    for (int y = y0; y < y1; ++y) {
+      const uint32_t* m = M.data() + We * (size_t)(y - y0 + 1) + 1;
+      uint8_t* o = dst + (int64_t)y * dp;
+      for (int x = 0; x < W; ++x) {
+        const int s = (int)(m[x] >> kCannySectorShift);
+        const ptrdiff_t d = (ptrdiff_t)canny_dy(s) * (ptrdiff_t)We + canny_dx(s);
+        o[x] = canny_class(m[x] & kCannyMagMask, m[x - d] & kCannyMagMask, m[x + d] & kCannyMagMask, s, lo, hi);
+      }
+    }
+  });
+}
+
+void cpu_hysteresis(const uint8_t* cls, int64_t cp, int W, int H, int conn, uint8_t* dst, int64_t dp, int threads) {
+  check_components(W, H, 1, conn);
+  STRIPE_CHECK(cls && dst, "canny: empty image");
+  STRIPE_CHECK(cp >= W && dp >= W, "canny: pitch smaller than a row");
+  std::vector<int32_t> labels((size_t)W * H);
+  const int N = cpu_components(cls, cp, W, H, conn, labels.data(), W, threads);
+  std::vector<uint8_t> strong((size_t)N + 1, 0);  // per label: the component holds a class 2 pixel
+  for (int y = 0; y < H; ++y) {
+    const uint8_t* c = cls + (int64_t)y * cp;
+    const int32_t* l = labels.data() + (size_t)y * W;
+    for (int x = 0; x < W; ++x)
+      if (c[x] >= 2) strong[(size_t)l[x]] = 1;
+  }
+  strong[0] = 0;
+  parallel_rows(0, H, 6 * (int64_t)W, std::max(1, threads), [&](int ya, int yb) {
+    for (int y = ya; y < yb; ++y) {
+      const int32_t* l = labels.data() + (size_t)y * W;
+      uint8_t* o = dst + (int64_t)y * dp;
+      for (int x = 0; x < W; ++x) o[x] = strong[(size_t)l[x]] ? 255 : 0;
+    }
+  });
+}
+
+void cpu_canny(const uint8_t* src, int64_t sp, int W, int H, int low, int high, CannyNorm norm, Border border,
+               uint8_t* dst, int64_t dp, int threads) {
+  check_canny(W, H, 1, low, high, (int)norm, border);
+  std::vector<uint8_t> cls((size_t)W * H);
+  cpu_canny_classes(src, sp, W, H, low, high, norm, border, cls.data(), W, threads);
+  cpu_hysteresis(cls.data(), W, W, H, 8, dst, dp, threads);
+}
+
+void cpu_hysteresis_threshold(const uint8_t* src, int64_t sp, int W, int H, int low, int high, int conn, uint8_t* dst,
+                              int64_t dp, int threads) {
+  check_hysteresis(W, H, 1, low, high, conn);
+  STRIPE_CHECK(src && dst, "canny: empty image");
+  STRIPE_CHECK(sp >= W && dp >= W, "canny: pitch smaller than a row");
+  std::vector<uint8_t> cls((size_t)W * H);
+  parallel_rows(0, H, 2 * (int64_t)W, std::max(1, threads), [&](int ya, int yb) {
+    for (int y = ya; y < yb; ++y) {
+      const uint8_t* s = src + (int64_t)y * sp;
+      uint8_t* c = cls.data() + (size_t)y * W;
+      for (int x = 0; x < W; ++x) c[x] = hysteresis_class(s[x], (uint32_t)low, (uint32_t)high);
+    }
+  });
+  cpu_hysteresis(cls.data(), W, W, H, conn, dst, dp, threads);
 }
 
 }  // namespace stripe

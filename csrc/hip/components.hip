@@ -22,6 +22,8 @@
 //                  atomicMin of the larger root onto the smaller).
 //   k_ccl_flatten  every pixel takes its root; the roots (slot == own index + 1)
 //                  are counted per row (__ballot / __popcll, one add a wave).
+//                  (These three are the forest passes; launch_ccl_forest queues them
+//                  alone for the hysteresis of canny.hip, which needs no numbers.)
 //   k_ccl_scan     one workgroup: the exclusive prefix of the H row counts, in
 //                  place, H + 1 entries; the last is N.
 //   k_ccl_number   one workgroup per row: a root's number is the row's prefix
@@ -543,11 +545,9 @@ unsigned grid_of(int64_t n, const char* what) {
   return (unsigned)n;
 }
 
-}  // namespace
-
-int launch_components_kernels(const ComponentsLaunch& L, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_ccl_mu);
-  uint32_t* tmp = ccl_temp(L.H);
+// The forest passes: the words cleared, k_ccl_tile, k_ccl_seam, k_ccl_flatten.  The caller holds g_ccl_mu and
+// goes on with the argument block returned (ntx: the row segments of kNT pixels).
+dev::CclArgs enqueue_forest(const ComponentsLaunch& L, uint32_t* tmp, hipStream_t s) {
   dev::CclArgs a{};
   a.src = L.src, a.lab = L.labels;
   a.sp = L.src_pitch, a.lp = L.labels_pitch;
@@ -555,7 +555,6 @@ int launch_components_kernels(const ComponentsLaunch& L, hipStream_t s) {
   a.conn8 = L.conn == 8;
   a.cap = (uint32_t)((int64_t)L.W * L.H + 2);
   a.rows = tmp;
-  uint32_t* n_word = tmp + L.H + 1;
   a.err = tmp + L.H + 2;
   HIP_CHECK(hipMemsetAsync(tmp, 0, ((size_t)L.H + 3) * sizeof(uint32_t), s));
   const int64_t tx = div_up(L.W, kCclTile), ty = div_up(L.H, kCclTile);
@@ -571,6 +570,25 @@ int launch_components_kernels(const ComponentsLaunch& L, hipStream_t s) {
   a.ntx = (int)segs;
   dev::k_ccl_flatten<<<grid_of(segs * L.H, "rows"), dev::kNT, 0, s>>>(a);
   HIP_CHECK(hipGetLastError());
+  return a;
+}
+
+}  // namespace
+
+CclForest launch_ccl_forest(const ComponentsLaunch& L, hipStream_t s) {
+  CclForest f;
+  f.lock = std::unique_lock<std::mutex>(g_ccl_mu);
+  const dev::CclArgs a = enqueue_forest(L, ccl_temp(L.H), s);
+  f.err = a.err, f.cap = a.cap;
+  return f;
+}
+
+int launch_components_kernels(const ComponentsLaunch& L, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_ccl_mu);
+  uint32_t* tmp = ccl_temp(L.H);
+  const dev::CclArgs a = enqueue_forest(L, tmp, s);
+  uint32_t* n_word = tmp + L.H + 1;
+  const int64_t segs = a.ntx;
   dev::k_ccl_scan<<<1, dev::kNT, 0, s>>>(tmp, L.H, n_word);
   HIP_CHECK(hipGetLastError());
   dev::k_ccl_number<<<grid_of(L.H, "rows"), dev::kNT, 0, s>>>(a);

@@ -287,6 +287,22 @@ void launch_window(const WindowLaunch& L, hipStream_t s) {
   launch_window_kernels(L, s);
 }
 
+void launch_canny(const CannyLaunch& L, hipStream_t s) {
+  // host-side shape checks before any kernel touches memory
+  STRIPE_CHECK(L.src && L.dst, "bad canny launch: null src or dst");
+  STRIPE_CHECK(L.stage >= 0 && L.stage <= (int)CannyStage::Hysteresis, "canny: unknown stage " << L.stage);
+  if (L.stage == (int)CannyStage::Hysteresis) {
+    check_hysteresis(L.W, L.H, 1, L.low, L.high, L.conn);
+  } else {
+    STRIPE_CHECK(L.border >= 0 && L.border <= (int)Border::Skip, "canny: unknown border " << L.border);
+    check_canny(L.W, L.H, 1, L.low, L.high, L.norm, (Border)L.border);
+  }
+  STRIPE_CHECK(L.src_pitch >= (int64_t)L.W, "canny: src_pitch " << L.src_pitch << " < row bytes " << L.W);
+  STRIPE_CHECK(L.dst_pitch >= (int64_t)L.W, "canny: dst_pitch " << L.dst_pitch << " < row bytes " << L.W);
+  (void)hipGetLastError();  // sticky errors of other libraries (see launch_pass)
+  launch_canny_kernels(L, s);
+}
+
 void launch_pass(const Pass& p, const PassConsts& pc, const PassLaunch& L, hipStream_t s) {
   // host-side shape checks before any kernel touches memory
   STRIPE_CHECK(L.in && L.out && L.W >= 1 && L.rows >= 0, "bad pass launch");

@@ -8,7 +8,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 
+#include "stripe/canny.h"
 #include "stripe/chain.h"
 #include "stripe/components.h"
 #include "stripe/distance.h"
@@ -471,6 +473,71 @@ void integral_device(const uint8_t* src, int64_t src_pitch, int W, int H, bool s
 void window_device(const uint8_t* src, int64_t src_pitch, int W, int H, int op, int K, int border, int C, int64_t kq,
                    uint8_t* dst, int64_t dst_pitch, hipStream_t s);
 void integral_release_scratch();  // frees the cached scratch of every device (waits for the devices)
+
+// The first three passes of the labelling (k_ccl_tile, k_ccl_seam, k_ccl_flatten)
+// on their own, for callers that need the forest but no numbering (the
+// hysteresis of canny.hip): queued on s, after which every foreground slot of
+// the label plane holds its root's raster index + 1 (the root its own) and the
+// background 0.  The call takes the components' cache lock and hands it over:
+// the caller queues its own kernels, reads *err back (non-zero: a union-find
+// loop overran its cap of `cap` steps), synchronises s once and only then lets
+// the lock go, the same contract as components_device.
+struct CclForest {
+  std::unique_lock<std::mutex> lock;
+  const uint32_t* err = nullptr;  // device
+  uint32_t cap = 0;
+};
+CclForest launch_ccl_forest(const ComponentsLaunch& L, hipStream_t s);  // components.hip; L is taken as checked
+
+// Canny edge detection and hysteresis thresholding of a 1-channel frame
+// (csrc/hip/canny.hip k_canny_*; the rule: stripe/canny.h).  Addressing as
+// k_orient: 64-bit on pitched views, the source pitch any value >= W at any
+// alignment, no byte outside a source row's W bytes read, nothing outside a
+// destination row's W bytes written.
+//
+// k_canny_nms<L2>: a workgroup per tile of kCannyTileX x kCannyTileY pixels.
+// The source goes once into LDS with a 2-pixel apron, the border applied at load
+// time; the magnitudes (with the sector in the top bits) of the tile plus a
+// 1-pixel apron go to LDS, 0 outside the frame; after a barrier every lane
+// classifies kCannyPixels pixels in a row and stores their class bytes
+// (canny_nms_lds_bytes()).  k_canny_classify is hysteresis_threshold's
+// pointwise class map.  The hysteresis runs launch_ccl_forest on the class
+// plane (class != 0 is foreground), then k_canny_mark (every class 2 pixel
+// stores -(r) into the slot of its root r - 1; all writers store the same
+// value, a reader takes |slot|) and k_canny_select (255 where the class is >= 1
+// and the root's slot is negative).  No kernel but k_canny_nms uses LDS.
+// The class plane (H rows of W bytes at a pitch rounded up to 4) and the forest
+// plane (W * H int32) are cached per device, stream and size until
+// canny_release_scratch.  canny_device and hysteresis_device synchronise the
+// stream once, to read the forest's error word; canny_classes_device does not.
+constexpr int kCannyTileX = 64;  // pixels of a tile of k_canny_nms across
+constexpr int kCannyTileY = 32;  // and down
+constexpr int kCannyPixels = 4;  // pixels in a row per lane (all k_canny_* kernels)
+constexpr int canny_nms_lds_bytes() {
+  return (kCannyTileX + 4) * (kCannyTileY + 4) + (kCannyTileX + 2) * (kCannyTileY + 2) * 4;  // source bytes, u32
+}
+enum class CannyStage : int { Canny = 0, Classes = 1, Hysteresis = 2 };
+struct CannyLaunch {
+  const uint8_t* src = nullptr;
+  int64_t src_pitch = 0;  // bytes
+  int W = 0, H = 0;
+  int stage = 0;          // CannyStage
+  int64_t low = 0, high = 0;
+  int norm = 0;           // CannyNorm (Canny, Classes)
+  int border = 0;         // Border (Canny, Classes)
+  int conn = 8;           // Hysteresis (Canny: 8)
+  uint8_t* dst = nullptr;
+  int64_t dst_pitch = 0;
+};
+void launch_canny(const CannyLaunch& L, hipStream_t s);          // dispatch.cpp: checks, then the kernels
+void launch_canny_kernels(const CannyLaunch& L, hipStream_t s);  // canny.hip
+void canny_device(const uint8_t* src, int64_t src_pitch, int W, int H, int low, int high, int norm, int border,
+                  uint8_t* dst, int64_t dst_pitch, hipStream_t s);
+void canny_classes_device(const uint8_t* src, int64_t src_pitch, int W, int H, int low, int high, int norm, int border,
+                          uint8_t* dst, int64_t dst_pitch, hipStream_t s);
+void hysteresis_device(const uint8_t* src, int64_t src_pitch, int W, int H, int low, int high, int conn, uint8_t* dst,
+                       int64_t dst_pitch, hipStream_t s);
+void canny_release_scratch();  // frees the cached scratch of every device (waits for the devices)
 
 // Write the x-margins of rows [y0, y1) of a stripe from its own pixels.
 void launch_fill_margins(uint8_t* origin, int64_t pitch, int W, int C, int y0, int y1, int px,

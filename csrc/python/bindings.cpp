@@ -1120,6 +1120,159 @@ PYBIND11_MODULE(_C, m) {
   m.attr("WINDOW_MAX_ABS_K") = kWindowMaxAbsK;
   m.attr("WINDOW_OPS") = std::vector<std::string>{"box", "std", "mean", "niblack", "sauvola"};
 
+  // ---- canny and hysteresis thresholding (stripe/canny.h); entry points of their own ----
+  // The host executor's calls take any uint8 array whose rows are packed (a strided view is read in place) and,
+  // with `out`, write into such a view.
+  struct U8View {
+    uint8_t* p;
+    int64_t pitch;
+    int W, H, C;
+  };
+  static const auto u8_view = [](const py::array& a, bool writable) {
+    STRIPE_CHECK(a.dtype().is(py::dtype::of<uint8_t>()), "canny: the image must be uint8");
+    STRIPE_CHECK(a.ndim() == 2 || a.ndim() == 3, "canny: the image must be HxW or HxWx1");
+    STRIPE_CHECK(!writable || a.writeable(), "canny: out is not writable");
+    U8View v{};
+    v.H = (int)a.shape(0), v.W = (int)a.shape(1), v.C = a.ndim() == 3 ? (int)a.shape(2) : 1;
+    // (C != 1 is refused by the caller's check, with the message every layer shares)
+    STRIPE_CHECK(v.C != 1 || ((v.W <= 1 || a.strides(1) == 1) && (v.H <= 1 || a.strides(0) >= v.W)),
+                 "canny: a row's pixels must be packed and the rows must not overlap");
+    v.p = static_cast<uint8_t*>(const_cast<void*>(a.data()));
+    v.pitch = v.H > 1 ? (int64_t)a.strides(0) : v.W;
+    return v;
+  };
+  static const auto u8_out = [](const py::object& out, int W, int H) {
+    if (out.is_none()) return py::array(py::array_t<uint8_t>(std::vector<py::ssize_t>{H, W}));
+    STRIPE_CHECK(py::isinstance<py::array>(out), "canny: out must be a numpy array");
+    py::array o = py::reinterpret_borrow<py::array>(out);
+    STRIPE_CHECK(o.ndim() == 2 && o.shape(0) == H && o.shape(1) == W, "canny: out must be " << H << "x" << W);
+    return o;
+  };
+  m.def("golden_canny", [](const U8Array& a, int low, int high, const std::string& norm, const std::string& border) {
+    const Image img = image_from_numpy(a);
+    const CannyNorm n = parse_canny_norm(norm);
+    const Border b = parse_border(border);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_canny(img, low, high, n, b);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("norm") = "l1", py::arg("border") = "reflect101",
+     "the u8 edge map (255 / 0): golden_canny_classes, then the flood fill from every class 2 pixel, 8-connected");
+  m.def("golden_canny_classes", [](const U8Array& a, int low, int high, const std::string& norm,
+                                   const std::string& border) {
+    const Image img = image_from_numpy(a);
+    const CannyNorm n = parse_canny_norm(norm);
+    const Border b = parse_border(border);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_canny_classes(img, low, high, n, b);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("norm") = "l1", py::arg("border") = "reflect101",
+     "the class plane (0 suppressed or weak, 1 weak candidate, 2 strong): the plain loops over the extended frame");
+  m.def("golden_hysteresis_threshold", [](const U8Array& a, int low, int high, int conn) {
+    const Image img = image_from_numpy(a);
+    Image out;
+    {
+      py::gil_scoped_release nogil;
+      out = golden_hysteresis_threshold(img, low, high, conn);
+    }
+    return image_to_numpy(out);
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("connectivity") = 8,
+     "255 where p > low and the pixel is connected through pixels > low to one > high, else 0");
+  m.def("cpu_canny", [view = u8_view, out_of = u8_out](const py::array& a, int low, int high, const std::string& norm,
+                                                      const std::string& border, int threads, const py::object& out) {
+    const U8View s = view(a, false);
+    const CannyNorm n = parse_canny_norm(norm);
+    const Border b = parse_border(border);
+    check_canny(s.W, s.H, s.C, low, high, (int)n, b);
+    py::array o = out_of(out, s.W, s.H);
+    const U8View d = view(o, true);
+    {
+      py::gil_scoped_release nogil;
+      cpu_canny(s.p, s.pitch, s.W, s.H, low, high, n, b, d.p, d.pitch, threads > 0 ? threads : cpu_threads());
+    }
+    return o;
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("norm") = "l1", py::arg("border") = "reflect101",
+     py::arg("threads") = 0, py::arg("out") = py::none(),
+     "canny on the host executor (row blocks, then cpu_components on the class plane); strided views are used in place");
+  m.def("cpu_canny_classes", [view = u8_view, out_of = u8_out](const py::array& a, int low, int high,
+                                                              const std::string& norm, const std::string& border,
+                                                              int threads, const py::object& out) {
+    const U8View s = view(a, false);
+    const CannyNorm n = parse_canny_norm(norm);
+    const Border b = parse_border(border);
+    check_canny(s.W, s.H, s.C, low, high, (int)n, b);
+    py::array o = out_of(out, s.W, s.H);
+    const U8View d = view(o, true);
+    {
+      py::gil_scoped_release nogil;
+      cpu_canny_classes(s.p, s.pitch, s.W, s.H, low, high, n, b, d.p, d.pitch, threads > 0 ? threads : cpu_threads());
+    }
+    return o;
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("norm") = "l1", py::arg("border") = "reflect101",
+     py::arg("threads") = 0, py::arg("out") = py::none(), "the class plane on the host executor");
+  m.def("cpu_hysteresis_threshold", [view = u8_view, out_of = u8_out](const py::array& a, int low, int high, int conn,
+                                                                     int threads, const py::object& out) {
+    const U8View s = view(a, false);
+    check_hysteresis(s.W, s.H, s.C, low, high, conn);
+    py::array o = out_of(out, s.W, s.H);
+    const U8View d = view(o, true);
+    {
+      py::gil_scoped_release nogil;
+      cpu_hysteresis_threshold(s.p, s.pitch, s.W, s.H, low, high, conn, d.p, d.pitch,
+                               threads > 0 ? threads : cpu_threads());
+    }
+    return o;
+  }, py::arg("image"), py::arg("low"), py::arg("high"), py::arg("connectivity") = 8, py::arg("threads") = 0,
+     py::arg("out") = py::none(), "hysteresis thresholding on the host executor");
+  m.def("canny_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int low, int high, const std::string& norm,
+                           const std::string& border, uintptr_t dst, int64_t dst_pitch, uintptr_t stream) {
+    const int n = (int)parse_canny_norm(norm), b = (int)parse_border(border);
+    py::gil_scoped_release nogil;
+    canny_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, low, high, n, b,
+                 reinterpret_cast<uint8_t*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("low"), py::arg("high"), py::arg("norm"),
+     py::arg("border"), py::arg("dst"), py::arg("dst_pitch"), py::arg("stream") = 0,
+     "k_canny_nms, the forest passes of k_ccl_*, k_canny_mark and k_canny_select on a pitched u8 device frame (any "
+     "alignment); returns after the call's one synchronisation of the stream");
+  m.def("canny_classes_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int low, int high,
+                                   const std::string& norm, const std::string& border, uintptr_t dst, int64_t dst_pitch,
+                                   uintptr_t stream) {
+    const int n = (int)parse_canny_norm(norm), b = (int)parse_border(border);
+    py::gil_scoped_release nogil;
+    canny_classes_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, low, high, n, b,
+                         reinterpret_cast<uint8_t*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("low"), py::arg("high"), py::arg("norm"),
+     py::arg("border"), py::arg("dst"), py::arg("dst_pitch"), py::arg("stream") = 0,
+     "k_canny_nms alone: the class plane; queued on the stream, no synchronisation");
+  m.def("hysteresis_device", [](uintptr_t src, int64_t src_pitch, int W, int H, int low, int high, int conn,
+                                uintptr_t dst, int64_t dst_pitch, uintptr_t stream) {
+    py::gil_scoped_release nogil;
+    hysteresis_device(reinterpret_cast<const uint8_t*>(src), src_pitch, W, H, low, high, conn,
+                      reinterpret_cast<uint8_t*>(dst), dst_pitch, as_stream(stream));
+  }, py::arg("src"), py::arg("src_pitch"), py::arg("W"), py::arg("H"), py::arg("low"), py::arg("high"),
+     py::arg("connectivity"), py::arg("dst"), py::arg("dst_pitch"), py::arg("stream") = 0,
+     "k_canny_classify, the forest passes, k_canny_mark and k_canny_select; returns after the call's one "
+     "synchronisation of the stream");
+  m.def("canny_release_scratch", [] {
+    py::gil_scoped_release nogil;
+    canny_release_scratch();
+  }, "free the cached device scratch of canny and hysteresis thresholding");
+  m.def("canny_tile", [] { return py::make_tuple(kCannyTileX, kCannyTileY); }, "k_canny_nms's tile: (tx, ty) pixels");
+  m.def("canny_lds", [] {
+    py::dict d;
+    d["k_canny_nms"] = canny_nms_lds_bytes();
+    for (const char* name : {"k_canny_classify", "k_canny_mark", "k_canny_select"}) d[name] = 0;
+    return d;
+  }, "LDS bytes of each k_canny_* kernel");
+  m.attr("CANNY_MAX_THRESHOLD") = kCannyMaxThreshold;
+  m.attr("HYSTERESIS_MAX_THRESHOLD") = kHysteresisMaxThreshold;
+  m.attr("CANNY_NORMS") = std::vector<std::string>{"l1", "l2"};
+
   // ---- histogram and the statistic ops' tables ----
   m.def("golden_histogram", [](const U8Array& a) { return hist_to_numpy(golden_histogram(image_from_numpy(a))); },
         py::arg("image"), "int64 counts of shape (C, 256)");

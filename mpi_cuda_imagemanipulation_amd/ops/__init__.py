@@ -1349,11 +1349,143 @@ def window_reference(x, op: str, ksize: int, border: str = "reflect101", c: int 
     return _reference_frame(x, lambda W, H: lambda arr: _builder(C.golden_window, arr, op, K, border, c, k))
 
 
+# ---- canny edges and hysteresis thresholding (csrc/include/stripe/canny.h) ----
+CANNY_NORMS = tuple(C.CANNY_NORMS)
+CANNY_MAX_THRESHOLD = int(C.CANNY_MAX_THRESHOLD)
+_CANNY_BORDERS = ("reflect101", "replicate", "constant")
+
+
+def _canny_shape(x):
+    """(W, H) of one 1-channel frame HxW or HxWx1; everything else is refused."""
+    if x.ndim == 4:
+        raise ValueError(f"canny: one frame at a time, got a batch of shape {tuple(x.shape)}")
+    if x.ndim == 3 and x.shape[2] == 3:
+        raise ValueError("canny: needs a 1-channel image, got C = 3; convert first (gray, threshold, ...)")
+    if not (x.ndim == 2 or (x.ndim == 3 and x.shape[2] == 1)):
+        raise ValueError(f"canny: the image must be HxW or HxWx1 uint8, got shape {tuple(x.shape)}")
+    W, H = int(x.shape[1]), int(x.shape[0])
+    if W < 1 or H < 1:
+        raise ValueError(f"canny: empty image ({W}x{H})")
+    if W * H > 2 ** 31 - 2:
+        raise ValueError(f"canny: {W}x{H} pixels exceed 2^31 - 2")
+    return W, H
+
+
+def _thresholds(low, high, limit):
+    """(low, high) as ints: any Python or numpy number whose value is integral, 0 <= low <= high <= limit."""
+    vals = []
+    for v in (low, high):
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+        if ok and isinstance(v, (float, np.floating)):
+            ok = bool(np.isfinite(v)) and float(v) == int(v)
+        vals.append(int(v) if ok else None)
+    if None in vals or not 0 <= vals[0] <= vals[1] <= limit:
+        raise ValueError(f"canny: the thresholds must be integers with 0 <= low <= high <= {limit}, "
+                         f"got low = {low!r}, high = {high!r}")
+    return vals[0], vals[1]
+
+
+def _canny_args(low, high, norm, border):
+    low, high = _thresholds(low, high, CANNY_MAX_THRESHOLD)
+    if norm not in CANNY_NORMS:
+        raise ValueError(f"canny: the norm must be l1 or l2, got {norm!r}")
+    if border not in _CANNY_BORDERS:
+        raise ValueError(f"canny: the border must be reflect101, replicate or constant, got {border!r}")
+    return low, high, norm, border
+
+
+def _edge_stage(x, W, H, device_call, host_call):
+    """One 1-channel frame through a C.*_device call (src, src_pitch, W, H, ..., dst, dst_pitch, stream) on torch's
+    current stream, or through the host executor; the u8 result has x's shape and container."""
+    if _is_tensor(x) and x.is_cuda:
+        xc = _device_mask(x, W)
+        out = torch.empty((H, W), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device)
+            device_call(xc.data_ptr(), xc.stride(0) if H > 1 else W, out.data_ptr(), W, stream.cuda_stream)
+        # keep the input alive until the stream has consumed it
+        xc.record_stream(stream)
+        return out[:, :, None] if x.ndim == 3 else out
+    out = host_call(_host_mask(x))
+    if x.ndim == 3:
+        out = out[:, :, None]
+    return torch.from_numpy(out) if _is_tensor(x) else out
+
+
+def canny(x, low, high, norm: str = "l1", border: str = "reflect101"):
+    """Canny edge detection: a u8 edge map, 255 on an edge, 0 elsewhere.
+
+    x: HxW or HxWx1 uint8.  The Sobel gradient (Gx, Gy; the frame extended by `border`: reflect101, replicate or
+    constant) gives the magnitude |Gx| + |Gy| (norm="l1", at most 2040) or Gx^2 + Gy^2 (norm="l2", compared with
+    low^2 and high^2; no root is taken); a pixel survives non-maximum suppression against its two neighbours
+    along the gradient (four sectors, integers only; of a two-pixel plateau exactly one pixel survives);
+    survivors above `high` are strong, those above `low` weak, and a weak pixel is kept iff it is 8-connected
+    through survivors to a strong one.  low, high: integers (any Python or numpy number whose value is
+    integral) with 0 <= low <= high <= 2040.  No blur is built in: chain `gaussian_blur` in front.  The rule:
+    stripe/canny.h.  A CUDA tensor runs on the k_canny_* HIP kernels and the union-find forest of k_ccl_* on
+    torch's current stream and gives a CUDA tensor (the call synchronises the stream once); numpy arrays / CPU
+    tensors run on the threaded host executor and keep their container.  Bit-identical to `canny_reference`."""
+    W, H = _canny_shape(x)
+    low, high, norm, border = _canny_args(low, high, norm, border)
+    return _edge_stage(
+        x, W, H,
+        lambda src, sp, dst, dp, s: _builder(C.canny_device, src, sp, W, H, low, high, norm, border, dst, dp, s),
+        lambda a: _builder(C.cpu_canny, a, low, high, norm, border))
+
+
+def canny_classes(x, low, high, norm: str = "l1", border: str = "reflect101"):
+    """The class plane of `canny` before the hysteresis, u8: 2 a strong pixel (it survives the suppression and its
+    magnitude is above high), 1 a weak one (above low), 0 everything else.  On a CUDA tensor the call queues
+    k_canny_nms and does not synchronise."""
+    W, H = _canny_shape(x)
+    low, high, norm, border = _canny_args(low, high, norm, border)
+    return _edge_stage(
+        x, W, H,
+        lambda src, sp, dst, dp, s: _builder(C.canny_classes_device, src, sp, W, H, low, high, norm, border, dst, dp, s),
+        lambda a: _builder(C.cpu_canny_classes, a, low, high, norm, border))
+
+
+def canny_reference(x, low, high, norm: str = "l1", border: str = "reflect101"):
+    """Golden CPU result of `canny` (numpy): plain loops over the extended frame, then a flood fill from every
+    strong pixel."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _canny_shape(arr)
+    low, high, norm, border = _canny_args(low, high, norm, border)
+    return _builder(C.golden_canny, _host_mask(arr), low, high, norm, border)
+
+
+def hysteresis_threshold(x, low, high, connectivity: int = 8):
+    """Hysteresis thresholding of a 1-channel frame: a u8 mask, 255 where p > low and the pixel is connected,
+    through pixels with p > low (connectivity 4 or 8), to a pixel with p > high; 0 elsewhere.  low, high:
+    integers with 0 <= low <= high <= 255.  Useful on `sobel` output or on `distance_transform(..., "u8")`.
+    Containers and streams as `canny`; bit-identical to `hysteresis_threshold_reference`."""
+    W, H = _canny_shape(x)
+    low, high = _thresholds(low, high, int(C.HYSTERESIS_MAX_THRESHOLD))
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f"canny: connectivity must be 4 or 8, got {connectivity!r}")
+    conn = int(connectivity)
+    return _edge_stage(
+        x, W, H,
+        lambda src, sp, dst, dp, s: _builder(C.hysteresis_device, src, sp, W, H, low, high, conn, dst, dp, s),
+        lambda a: _builder(C.cpu_hysteresis_threshold, a, low, high, conn))
+
+
+def hysteresis_threshold_reference(x, low, high, connectivity: int = 8):
+    """Golden CPU result of `hysteresis_threshold` (numpy): a flood fill from every pixel above high."""
+    arr = x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+    _canny_shape(arr)
+    low, high = _thresholds(low, high, int(C.HYSTERESIS_MAX_THRESHOLD))
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (4, 8):
+        raise ValueError(f"canny: connectivity must be 4 or 8, got {connectivity!r}")
+    return _builder(C.golden_hysteresis_threshold, _host_mask(arr), low, high, int(connectivity))
+
+
 def clear_cache() -> None:
     with _cache_lock:
         _engines.clear()
     C.distance_release_scratch()
     C.integral_release_scratch()
+    C.canny_release_scratch()
 
 
 __all__ = [
@@ -1375,4 +1507,6 @@ __all__ = [
     "DISTANCE_NONE", "DISTANCE_OUTPUTS",
     "integral", "integral_reference", "box_filter", "local_std", "local_threshold", "window_reference",
     "WINDOW_OPS", "WINDOW_MAX_K", "WINDOW_MAX_K_SQUARES", "LOCAL_THRESHOLD_METHODS",
+    "canny", "canny_reference", "canny_classes", "hysteresis_threshold", "hysteresis_threshold_reference",
+    "CANNY_NORMS", "CANNY_MAX_THRESHOLD",
 ]

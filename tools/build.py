@@ -55,6 +55,7 @@ CORE_SOURCES = [
     "core/components.cpp",
     "core/distance.cpp",
     "core/integral.cpp",
+    "core/canny.cpp",
     "hip/pointwise.hip",
     "hip/stencil.hip",
     "hip/stencil_inst_a.hip",
@@ -75,6 +76,7 @@ CORE_SOURCES = [
     "hip/components.hip",
     "hip/distance.hip",
     "hip/integral.hip",
+    "hip/canny.hip",
     "hip/dispatch.cpp",
     "runtime/comm_rccl.cpp",
     "runtime/comm_local.cpp",
